@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark: Mvoxels/s per RL iteration of the multiview deconvolution path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -20,7 +20,17 @@ Two ways to drive N GPUs, both one slab per GPU:
     than N visible GPUs is an error (rc != 0), never a silent 1-GPU run.
   * torchrun (RANK set): one process per GPU, halos over RCCL send/recv.
 
-Also reported: ``roofline`` of the dominant engine pass (largest total time;
+A plain run sets up, warms up, times the K steps, writes its outputs if
+``--dump-outputs DIR`` is given and prints the result line; the extra keys below
+are null.  ``--dump-outputs DIR`` writes what the timed ``Session.run`` left after
+its last step: ``DIR/psi.npy`` (float32; the whole estimate, or a fixed seeded
+sample of the voxels of a large one) and ``DIR/stats.npy`` (float64, the last
+step's per-view statistics as ``run`` returns them); under a launcher every rank
+writes ``psi_rank<r>.npy`` and ``stats_rank<r>.npy`` for its slab.  The inputs are
+seeded, so the same arguments give the same inputs.
+
+With ``--full`` also reported (each can be switched off again with its ``--no-*``
+option): ``roofline`` of the dominant engine pass (largest total time;
 algorithmic bytes per launch in DESIGN.md "Kernels") timed with HIP events on
 the session's stream, ``roofline_iteration`` (whole iteration against the
 engine's compulsory traffic), ``default_mode`` (the reference default
@@ -62,6 +72,12 @@ def parse(argv=None):
     ap.add_argument("--psftype", default="INDEPENDENT")
     ap.add_argument("--lam", type=float, default=0.0)
     ap.add_argument("--fp16", action="store_true", help="fp16 img/weight storage")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline: default_mode, the HIP-event roofline / "
+                         "kernel_ms pass, the strong and legacy lines and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write psi (a seeded sample of a large volume) and the last "
+                         "step's statistics to DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-size", type=int, default=384,
                     help="edge of the CPU-baseline sample cube (same views, PSFs and mode)")
@@ -94,6 +110,8 @@ def parse(argv=None):
                     help="BASELINE configs[2] per rank: the 1024x128x512 y-slab one of 8 ranks holds "
                          "(padded 1050x540x152 internally), EFFICIENT_BAYESIAN 0.006")
     a = ap.parse_args(argv)
+    if not a.full:   # a plain run measures the headline only
+        a.no_cpu_baseline = a.no_timing = a.no_strong_line = a.no_legacy_line = a.no_default_mode = True
     if a.c3_rank:
         a.shape = [1024, 128, 512]
         a.slab_axis = "y"
@@ -308,6 +326,25 @@ def slab_geom(sess, nslabs, ngpus):
             "nz_int": ext[2], "Mz": M[2], "kplanes": sess.kernel_planes(0), "nslabs": nslabs, "ngpus": ngpus}
 
 
+DUMP_BUDGET = 32 << 20   # bytes of psi per run, all ranks together
+DUMP_SEED = 20240607     # of the flat sample indices of a psi above the budget
+
+
+def dump_outputs(path, sess, stats, rank, world):
+    """What a caller of the timed path holds after its last step, as .npy files: psi
+    (float32; above the budget the voxels at sorted flat indices drawn from a fixed
+    seed, so two builds are compared voxel for voxel) and the last step's statistics
+    (float64, views x 2)."""
+    os.makedirs(path, exist_ok=True)
+    tag = f"_rank{rank}" if world > 1 else ""
+    psi = sess.get_psi().reshape(-1)
+    keep = DUMP_BUDGET // 4 // world
+    if psi.size > keep:
+        psi = psi[np.sort(np.random.default_rng(DUMP_SEED).integers(0, psi.size, size=keep))]
+    np.save(os.path.join(path, f"psi{tag}.npy"), np.ascontiguousarray(psi, np.float32))
+    np.save(os.path.join(path, f"stats{tag}.npy"), np.asarray(stats[-1] if len(stats) else stats, np.float64))
+
+
 def legacy_line(args, rank, world, local, dist, broadcast_comm_id, barrier, max_over_ranks, edge=512, iters=3):
     """LucyRichardsonMultiViewDeconvolution (:24-358) through lrsim_*: V = world views of
     edge^3 (view v on rank v % world, generated from its own seed on the rank that owns it),
@@ -451,17 +488,17 @@ def main(argv=None):
     def timed(s, lam, steps, warmup):
         """W warm-up iterations (untimed), then K iterations between barriers and
         device syncs (every GPU of the session: Session.run returns after all of its
-        device groups finished); the max over ranks."""
+        device groups finished); the max over ranks, and what the timed run returned."""
         if warmup:
             s.run(warmup, lam)
         barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        s.run(steps, lam)
+        stats = s.run(steps, lam)
         torch.cuda.synchronize()
         t = time.perf_counter() - t0
         barrier()
-        return max_over_ranks(t)
+        return max_over_ranks(t), stats
 
     def placement(s):
         """devices, slabs and the engine pass each slab ran (fast: x pass 2, z pass 3);
@@ -480,8 +517,10 @@ def main(argv=None):
 
     wb = 2 if args.fp16 else 4
 
-    def measure(s, dims_g, lam, steps, warmup, want_timing):
-        t = timed(s, lam, steps, warmup)
+    def measure(s, dims_g, lam, steps, warmup, want_timing, dump=None):
+        t, stats = timed(s, lam, steps, warmup)
+        if dump:   # before the timing pass iterates further
+            dump_outputs(dump, s, stats, rank, world)
         out = {"value": round(dims_g[0] * dims_g[1] * dims_g[2] * steps / t / 1e6, 2),
                "ms_per_step": round(t / max(steps, 1) * 1e3, 3)}
         if want_timing and not args.no_timing:
@@ -493,7 +532,10 @@ def main(argv=None):
 
     # ---- headline (weak, or --strong) and the reference-default mode on the same views
     shape = args.shape if args.shape else (args.size,) * 3
+    # (index_add_ of the bead splats: a fixed summation order, so the inputs repeat bit for bit)
+    torch.use_deterministic_algorithms(True, warn_only=True)
     dims, dims_g, axis, imgs, ws, psfs, kw = build_case(shape, args.strong)
+    torch.use_deterministic_algorithms(False)
     default_mode = None
     if not args.no_default_mode and not (args.psftype == "OPTIMIZATION_I" and args.lam == 0.006):
         with make_session(dims, kw, imgs, ws, psfs, "OPTIMIZATION_I") as s2:
@@ -503,7 +545,7 @@ def main(argv=None):
     sess = make_session(dims, kw, imgs, ws, psfs, args.psftype)
     del imgs, ws
     torch.cuda.empty_cache()
-    head = measure(sess, dims_g, args.lam, args.steps, args.warmup, True)
+    head = measure(sess, dims_g, args.lam, args.steps, args.warmup, True, args.dump_outputs)
     place = placement(sess)
     M = sess.fft_dims(0)
     sess.close()

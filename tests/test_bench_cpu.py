@@ -61,6 +61,54 @@ def test_c5_rank_preset():
     assert a.no_strong_line and a.no_default_mode
 
 
+EXTRAS = ("no_cpu_baseline", "no_timing", "no_strong_line", "no_legacy_line", "no_default_mode")
+
+
+def test_plain_run_measures_the_headline_only():
+    """Without --full every extra measurement is off; --full brings them back and each
+    --no-* option still takes its own away."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.dump_outputs) == (7, 2, None)
+    assert all(getattr(a, k) for k in EXTRAS)
+    f = bench.parse(["--full"])
+    assert not any(getattr(f, k) for k in EXTRAS)
+    g = bench.parse(["--full", "--no-cpu-baseline", "--no-strong-line"])
+    assert [getattr(g, k) for k in EXTRAS] == [True, False, True, False, False]
+
+
+class _FakeSession:
+    def __init__(self, psi):
+        self.psi = psi
+
+    def get_psi(self):
+        return self.psi.copy()
+
+
+def test_dump_outputs_small_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: a small psi whole, a large one as the same seeded sample every
+    time (float32), the last step's statistics as float64."""
+    import numpy as np
+
+    psi = np.arange(4 * 5 * 6, dtype=np.float32).reshape(4, 5, 6)
+    stats = np.arange(3 * 2 * 2, dtype=np.float64).reshape(3, 2, 2)
+    bench.dump_outputs(str(tmp_path / "a"), _FakeSession(psi), stats, 0, 1)
+    got = np.load(tmp_path / "a" / "psi.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, psi.reshape(-1))
+    st = np.load(tmp_path / "a" / "stats.npy")
+    assert st.dtype == np.float64 and np.array_equal(st, stats[-1])
+
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4 * 16)   # 16 voxels of the 120
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), _FakeSession(psi), stats, 0, 1)
+    b, c = np.load(tmp_path / "b" / "psi.npy"), np.load(tmp_path / "c" / "psi.npy")
+    assert b.shape == (16,) and b.dtype == np.float32 and np.array_equal(b, c)
+    assert np.all(np.diff(b) >= 0) and set(b.tolist()) <= set(psi.reshape(-1).tolist())
+    # under a launcher every rank writes its own files and shares the budget
+    bench.dump_outputs(str(tmp_path / "r"), _FakeSession(psi), stats, 1, 2)
+    assert np.load(tmp_path / "r" / "psi_rank1.npy").shape == (8,)
+    assert (tmp_path / "r" / "stats_rank1.npy").exists()
+
+
 def test_engine_classes_pointwise_bytes():
     """The iteration model counts (12 + 2w) N + (32 + 4y + 2z) S bytes per view; the
     exchange-window class carries no bytes (it is a time, not a pass)."""

@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 i=0
 for e in "$@"; do
   [ "$e" = "-" ] && e=""
-  env $e timeout -k 10 200 python3 bench.py --steps 5 --no-cpu-baseline > $OUT/ab_$i.log 2>&1 || exit 1
+  env $e timeout -k 10 200 python3 bench.py --full --steps 5 --no-cpu-baseline > $OUT/ab_$i.log 2>&1 || exit 1
   tail -1 $OUT/ab_$i.log > $OUT/ab_$i.json
   i=$((i+1))
 done

@@ -16,7 +16,7 @@ declare -A CFG=(
 NAMES=${@:-c2_4view_512 c3_1024x1024x512 c3_zslab_of8 c3_yslab_of8 c5_fp16_slab c4_rl_768 v6_1024cube_2slabs}
 for n in $NAMES; do
   echo "== $n: ${CFG[$n]}"
-  timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-default-mode ${CFG[$n]} > $OUT/$n.log 2>&1 || exit $?
+  timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-default-mode ${CFG[$n]} > $OUT/$n.log 2>&1 || exit $?
   tail -1 $OUT/$n.log > $OUT/$n.json
   python3 -c "import json; d=json.load(open('$OUT/$n.json')); print('$n', d['value'], 'Mvox/s', d['ms_per_step'], 'ms', d['config']['fft_dims_xyz'], 'roof', d['roofline']['kernel'], d['roofline']['frac'])"
 done

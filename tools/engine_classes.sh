@@ -15,7 +15,7 @@ declare -A CFG=(
   [c3rank]="--c3-rank --steps 6 --warmup 2"
 )
 for n in ${CLASSES:-headline c3 c3x8 c3rank c4 c5}; do
-  timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-legacy-line ${CFG[$n]} > $OUT/$n.log 2>&1 || { echo "$n failed"; tail -5 $OUT/$n.log; exit 1; }
+  timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-legacy-line ${CFG[$n]} > $OUT/$n.log 2>&1 || { echo "$n failed"; tail -5 $OUT/$n.log; exit 1; }
   tail -1 $OUT/$n.log > $OUT/$n.json
   python3 - $OUT/$n.json $n <<'PY'
 import json, sys
