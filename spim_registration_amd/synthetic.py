@@ -26,8 +26,7 @@ def rng_for(config_id: int):
     return np.random.default_rng(SEED0 + int(config_id))
 
 
-def psf(view: int, num_views: int, size=(25, 25, 25), sigma=(1.2, 1.2, 3.5)) -> np.ndarray:
-    """[z, y, x] PSF of view ``view`` (odd ``size`` = (kx, ky, kz))."""
+def _psf64(view: int, num_views: int, size, sigma) -> np.ndarray:
     kx, ky, kz = size
     th = math.radians(view * 180.0 / max(num_views, 1))
     z, y, x = np.meshgrid(np.arange(kz) - kz // 2, np.arange(ky) - ky // 2, np.arange(kx) - kx // 2,
@@ -38,7 +37,34 @@ def psf(view: int, num_views: int, size=(25, 25, 25), sigma=(1.2, 1.2, 3.5)) -> 
     sx, sy, sz = sigma
     g = np.exp(-0.5 * ((xr / sx) ** 2 + (y / sy) ** 2 + (zr / sz) ** 2))
     g /= g.sum()
-    return g.astype(np.float32)
+    return g
+
+
+def psf(view: int, num_views: int, size=(25, 25, 25), sigma=(1.2, 1.2, 3.5)) -> np.ndarray:
+    """[z, y, x] PSF of view ``view`` (odd ``size`` = (kx, ky, kz))."""
+    return _psf64(view, num_views, size, sigma).astype(np.float32)
+
+
+def psf_asymmetric(view: int, num_views: int, size=(25, 25, 25), seed: int = 0,
+                   sigma=(1.2, 1.2, 3.5)) -> np.ndarray:
+    """[z, y, x] PSF without any symmetry (odd ``size`` = (kx, ky, kz)), as kernels
+    extracted from beads are: ``psf`` times a linear ramp (1 + a z)(1 + a y)(1 + a x) over
+    [-1, 1] per axis (|a| uniform in [0.3, 0.8], random sign) times a log-normal speckle
+    (sigma 0.35, so the kernel is not separable), sum 1.  The kernel differs from its
+    point reflection and from its mirror image along every axis, and its spectrum has an
+    imaginary part -- ``psf`` has neither property.  All taps stay positive as long as
+    the Gaussian's tail does not underflow float32 (grids beyond about 13 sigma need a
+    wider ``sigma``)."""
+    rng = np.random.default_rng(9000 + 17 * int(seed) + int(view))
+    k = _psf64(view, num_views, size, sigma)
+    for ax in range(3):
+        a = rng.uniform(0.3, 0.8) * rng.choice([-1.0, 1.0])
+        shp = [1, 1, 1]
+        shp[ax] = k.shape[ax]
+        k = k * (1.0 + a * np.linspace(-1.0, 1.0, k.shape[ax]).reshape(shp))
+    k = k * np.exp(0.35 * rng.standard_normal(k.shape))
+    k /= k.sum()
+    return k.astype(np.float32)
 
 
 def truth_volume(shape, rng, bead_density=1.0 / 16 ** 3) -> np.ndarray:
@@ -82,16 +108,17 @@ def blend_weight(shape, view: int, num_views: int) -> np.ndarray:
 
 def make_views(shape, num_views: int, config_id: int = 0, ksize=(25, 25, 25),
                weights: str = "blend", partial: bool = False, bead_density=1.0 / 16 ** 3,
-               photons: float = 1000.0):
+               photons: float = 1000.0, asymmetric: bool = False):
     """Returns (imgs, weights, psfs, truth); shape = (nz, ny, nx).
 
     ``weights``: 'blend' (VIRTUAL-normalised cosine blending) or 'ones'.
-    ``partial``: view 0 has no data (img = 0, w = 0) in its last third along z."""
+    ``partial``: view 0 has no data (img = 0, w = 0) in its last third along z.
+    ``asymmetric``: the views are blurred with ``psf_asymmetric`` instead of ``psf``."""
     rng = rng_for(config_id)
     truth = truth_volume(shape, rng, bead_density)
     imgs, ws, psfs = [], [], []
     for v in range(num_views):
-        k = psf(v, num_views, ksize)
+        k = psf_asymmetric(v, num_views, ksize) if asymmetric else psf(v, num_views, ksize)
         psfs.append(k)
         blurred = scipy.signal.fftconvolve(np.pad(truth, [(s // 2, s // 2) for s in k.shape], mode="reflect"),
                                            k.astype(np.float64), mode="valid")

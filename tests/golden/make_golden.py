@@ -1,6 +1,10 @@
 """Generates the committed golden vectors under tests/golden/ from the oracle.
 
-    python tests/golden/make_golden.py
+    python tests/golden/make_golden.py [name ...]
+
+Without names every vector is rewritten; with names (file stems, e.g.
+``rl_asym_independent conv``) only those, so the other committed files keep their bytes
+(an .npz carries the time it was written).
 
 PARITY UNPINNED: the Java reference cannot run in this container (no JVM, no
 ImgLib2 jars) and ships no fixtures, so these vectors come
@@ -28,13 +32,20 @@ RL_CASES = [
     ("rl_opt1_tikhonov_partial", (16, 18, 20), 3, (5, 7, 9), ref.PSFTYPE.OPTIMIZATION_I, 4, 0.006, "blend", True, 8),
     ("rl_opt2_T4", (14, 16, 18), 3, (7, 5, 9), ref.PSFTYPE.OPTIMIZATION_II, 3, 0.006, "blend", False, 4),
     ("rl_bayes_T1", (14, 16, 18), 3, (5, 5, 7), ref.PSFTYPE.EFFICIENT_BAYESIAN, 3, 0.006, "blend", True, 1),
+    # asymmetric, non-separable PSFs (synthetic.psf_asymmetric): inverted_kernel is not the
+    # identity and the kernel spectra are complex (tests/test_asym_cpu.py)
+    ("rl_asym_independent", (16, 18, 20), 2, (5, 7, 9), ref.PSFTYPE.INDEPENDENT, 4, 0.0, "ones", False, 8),
+    ("rl_asym_bayes_partial", (14, 16, 18), 3, (5, 5, 7), ref.PSFTYPE.EFFICIENT_BAYESIAN, 3, 0.006, "blend", True, 8),
 ]
 
 
-def make_rl():
+def make_rl(only=None):
     for i, (name, shape, V, ks, pt, iters, lam, wt, partial, T) in enumerate(RL_CASES):
+        if only and name not in only:
+            continue
         imgs, ws, psfs, _ = synthetic.make_views(shape, V, config_id=100 + i, ksize=ks, weights=wt,
-                                                 partial=partial, bead_density=1.0 / 6 ** 3)
+                                                 partial=partial, bead_density=1.0 / 6 ** 3,
+                                                 asymmetric=name.startswith("rl_asym"))
         k1, k2 = ref.prepare_kernels(psfs, pt, T)
         res = ref.mv_deconvolution(imgs, ws, psfs, pt, iters, lam, ij_threads=T)
         np.savez_compressed(os.path.join(HERE, name + ".npz"),
@@ -69,7 +80,13 @@ def make_dog():
 
 
 if __name__ == "__main__":
-    make_rl()
-    make_conv()
-    make_dog()
+    only = set(sys.argv[1:])
+    unknown = only - {c[0] for c in RL_CASES} - {"conv", "dog"}
+    if unknown:
+        sys.exit("unknown golden vector(s): " + " ".join(sorted(unknown)))
+    make_rl(only)
+    if not only or "conv" in only:
+        make_conv()
+    if not only or "dog" in only:
+        make_dog()
     print("golden vectors written to", HERE)

@@ -69,6 +69,28 @@ def test_separable_convolve_n(gpu, oob, sigmas):
     np.testing.assert_array_equal(im.reshape(img.shape), exp)
 
 
+@pytest.mark.parametrize("taps", [7, 15])
+@pytest.mark.parametrize("oob", [legacy.OutOfBounds.ZERO, legacy.OutOfBounds.VALUE,
+                                 legacy.OutOfBounds.EXTEND_BORDER_PIXELS, legacy.OutOfBounds.MIRROR_SINGLE])
+def test_separable_convolve_n_asymmetric_taps(gpu, oob, taps):
+    """Gaussian taps cannot tell a reversed tap order.  Random positive taps, different per
+    axis: convolve_N applies them in correlation form, out[i] = sum_j in[i + j - r] * k[j]
+    (dog_ref.convolve_axis), bit for bit."""
+    rng = np.random.default_rng(7)
+    img = rng.random((13, 17, 19)).astype(np.float32)
+    ks = [(rng.random(taps) + 0.05).astype(np.float32) for _ in range(3)]      # x, y, z
+    for k in ks:
+        assert np.abs(k - k[::-1]).max() > 0.1
+    cuda = legacy.CUDASeparableConvolution()
+    im = img.copy().reshape(-1)
+    assert cuda._conv(taps, im, ks[0], ks[1], ks[2], 19, 17, 13, True, True, True, int(oob), 0.25, 0)
+    mode = {0: "zero", 1: "value", 2: "border", 3: "mirror"}[int(oob)]
+    exp = dog_ref.gauss3d(img, ks, mode, 0.25)
+    np.testing.assert_array_equal(im.reshape(img.shape), exp)
+    flipped = dog_ref.gauss3d(img, [k[::-1] for k in ks], mode, 0.25)
+    assert rel_l2(flipped, exp) > 1e-2            # (the taps can tell)
+
+
 def test_separable_convolve_bad_device(gpu):
     cuda = legacy.CUDASeparableConvolution()
     im = np.ones(27, np.float32)
