@@ -22,12 +22,15 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
 
+import golden_io  # noqa: E402
 from oracle import dog_ref, mvdecon_ref as ref  # noqa: E402
 from spim_registration_amd import synthetic  # noqa: E402
 
 RL_CASES = [
-    # name, shape (z,y,x), views, ksize (x,y,z), psftype, iters, lambda, weights, partial, T
+    # name, shape (z,y,x), views, ksize (x,y,z) or a list of one per view, psftype, iters, lambda, weights,
+    # partial, T
     ("rl_independent_l0", (16, 18, 20), 2, (5, 7, 9), ref.PSFTYPE.INDEPENDENT, 4, 0.0, "ones", False, 8),
     ("rl_opt1_tikhonov_partial", (16, 18, 20), 3, (5, 7, 9), ref.PSFTYPE.OPTIMIZATION_I, 4, 0.006, "blend", True, 8),
     ("rl_opt2_T4", (14, 16, 18), 3, (7, 5, 9), ref.PSFTYPE.OPTIMIZATION_II, 3, 0.006, "blend", False, 4),
@@ -36,24 +39,35 @@ RL_CASES = [
     # identity and the kernel spectra are complex (tests/test_asym_cpu.py)
     ("rl_asym_independent", (16, 18, 20), 2, (5, 7, 9), ref.PSFTYPE.INDEPENDENT, 4, 0.0, "ones", False, 8),
     ("rl_asym_bayes_partial", (14, 16, 18), 3, (5, 5, 7), ref.PSFTYPE.EFFICIENT_BAYESIAN, 3, 0.006, "blend", True, 8),
+    # asymmetric PSFs of a different size per view, none the largest on every axis: the compound kernels are
+    # "same"-size in each view's own dims and the session's halo is a mix of views (tests/test_gpu_rl_long.py);
+    # the views are blurred with MIXED_BLUR-sized kernels, RL runs with the listed ones
+    ("rl_mixed_ksize", (10, 12, 14), 3, [(5, 7, 9), (9, 3, 5), (3, 9, 7)], ref.PSFTYPE.OPTIMIZATION_I, 3, 0.006,
+     "blend", True, 8),
 ]
+MIXED_BLUR = (5, 5, 5)
 
 
 def make_rl(only=None):
     for i, (name, shape, V, ks, pt, iters, lam, wt, partial, T) in enumerate(RL_CASES):
         if only and name not in only:
             continue
-        imgs, ws, psfs, _ = synthetic.make_views(shape, V, config_id=100 + i, ksize=ks, weights=wt,
-                                                 partial=partial, bead_density=1.0 / 6 ** 3,
-                                                 asymmetric=name.startswith("rl_asym"))
+        mixed = isinstance(ks, list)
+        imgs, ws, psfs, _ = synthetic.make_views(shape, V, config_id=100 + i, ksize=MIXED_BLUR if mixed else ks,
+                                                 weights=wt, partial=partial, bead_density=1.0 / 6 ** 3,
+                                                 asymmetric=mixed or name.startswith("rl_asym"))
+        if mixed:
+            psfs = [synthetic.psf_asymmetric(v, V, ks[v]) for v in range(V)]
+        stack = golden_io.stack if mixed else np.stack
+        extra = {"kdims": np.array([k.shape for k in psfs], np.int32)} if mixed else {}
         k1, k2 = ref.prepare_kernels(psfs, pt, T)
         res = ref.mv_deconvolution(imgs, ws, psfs, pt, iters, lam, ij_threads=T)
         np.savez_compressed(os.path.join(HERE, name + ".npz"),
-                            imgs=np.stack(imgs), weights=np.stack(ws), psfs=np.stack(psfs),
-                            k1=np.stack(k1), k2=np.stack(k2), psi=res.psi,
+                            imgs=np.stack(imgs), weights=np.stack(ws), psfs=stack(psfs),
+                            k1=stack(k1), k2=stack(k2), psi=res.psi,
                             stats=np.array(res.stats, np.float64), avg=np.float64(res.avg),
                             psftype=np.int32(pt), iters=np.int32(iters), lam=np.float64(lam),
-                            ij_threads=np.int32(T))
+                            ij_threads=np.int32(T), **extra)
 
 
 def make_conv():

@@ -33,6 +33,7 @@ GOLD = os.path.join(ROOT, "tests", "golden")
 
 import numpy as np  # noqa: E402
 
+import golden_io  # noqa: E402  (numpy only)
 from oracle import dog_ref  # noqa: E402  (numpy-only checker)
 from spim_registration_amd import _lib, dog, legacy  # noqa: E402
 from spim_registration_amd.decon import PSFTYPE, Session  # noqa: E402
@@ -95,7 +96,8 @@ def main() -> int:
 
     for path in sorted(glob.glob(os.path.join(GOLD, "rl_*.npz"))):
         g = np.load(path)
-        imgs, ws, psfs = g["imgs"], g["weights"], g["psfs"]
+        imgs, ws = g["imgs"], g["weights"]
+        psfs, gk1, gk2 = (golden_io.kernels(g, n) for n in ("psfs", "k1", "k2"))   # per-view dims
         nz, ny, nx = imgs.shape[1:]
         with Session((nx, ny, nz), ij_threads=int(g["ij_threads"])) as s:
             for i, w, k in zip(imgs, ws, psfs):
@@ -104,7 +106,7 @@ def main() -> int:
             ek = 0.0                      # kernels: 1e-6 (K1) and 1e-5 (K2) as test_gpu_golden.py
             for v in range(len(psfs)):
                 k1, k2 = s.get_kernels(v, psfs[v].shape)
-                ek = max(ek, rel_l2(k1, g["k1"][v]), rel_l2(k2, g["k2"][v]) / 10)
+                ek = max(ek, rel_l2(k1, gk1[v]), rel_l2(k2, gk2[v]) / 10)
             avg = s.init_psi()
             st = s.run(int(g["iters"]), float(g["lam"]))
             s.apply_mask()

@@ -32,7 +32,8 @@ def asym_psf(view, num_views, size):
     return synthetic.psf_asymmetric(view, num_views, size)
 
 
-# (num_views, ksize) of every kernel set the GPU tests and the golden fixtures use
+# (num_views, ksize) of every kernel set the GPU tests and the golden fixtures use (the sets
+# with one size per view, and the 4- and 6-view ones: tests/test_rl_long_cpu.py)
 PSF_SETS = [
     (3, (7, 9, 11)), (3, (9, 7, 11)), (3, (5, 9, 7)),        # kernel preparation, whole RL, lrsim
     (4, (31, 19, 31)), (4, (25, 19, 21)),                    # block-parallel compound kernels

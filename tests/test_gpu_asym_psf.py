@@ -38,6 +38,7 @@ TOL = 1e-4
 MAXNORM_K = 4
 
 OPT1 = PSFTYPE.OPTIMIZATION_I
+MIXED_BLUR = (5, 5, 5)     # the common blur of the views of a case with per-view kernel sizes
 
 
 def max_err(a, b):
@@ -47,11 +48,20 @@ def max_err(a, b):
 
 @functools.lru_cache(maxsize=None)
 def case(shape, ksize, V=2, cid=7, weights="blend", partial=True, fp16=False):
-    """Views blurred with the asymmetric kernels (read-only; shared between tests)."""
-    imgs, ws, ks, _ = synthetic.make_views(shape, V, config_id=cid, ksize=ksize, weights=weights,
-                                           partial=partial, bead_density=1.0 / 6 ** 3, asymmetric=True)
+    """Views blurred with the asymmetric kernels (read-only; shared between tests).
+    ``ksize``: one (kx, ky, kz) for every view, or a tuple of V of them (per-view kernel
+    sizes: the views are blurred with MIXED_BLUR-sized kernels and RL runs with the
+    given ones, tests/test_gpu_rl_long.py)."""
+    mixed = isinstance(ksize[0], tuple)
+    imgs, ws, ks, _ = synthetic.make_views(shape, V, config_id=cid, ksize=MIXED_BLUR if mixed else ksize,
+                                           weights=weights, partial=partial, bead_density=1.0 / 6 ** 3,
+                                           asymmetric=True)
+    sizes = ksize if mixed else (ksize,) * V
+    assert len(sizes) == V
+    if mixed:
+        ks = [asym_psf(v, V, sizes[v]) for v in range(V)]
     for v, k in enumerate(ks):
-        assert np.array_equal(k, asym_psf(v, V, ksize))      # the kernels test_asym_cpu.py checks
+        assert np.array_equal(k, asym_psf(v, V, sizes[v]))   # the kernels test_asym_cpu.py checks
     if fp16:   # the oracle runs on the fp16-rounded inputs the session stores
         imgs = [i.astype(np.float16).astype(np.float32) for i in imgs]
         ws = [w.astype(np.float16).astype(np.float32) for w in ws]

@@ -12,6 +12,7 @@ import os
 import numpy as np
 import pytest
 
+import golden_io
 from conftest import rel_l2
 from oracle import dog_ref, mvdecon_ref as ref
 from spim_registration_amd import legacy, synthetic
@@ -24,10 +25,12 @@ def test_oracle_reproduces_golden_rl(path):
     g = np.load(path)
     pt = ref.PSFTYPE(int(g["psftype"]))
     T = int(g["ij_threads"])
-    psfs = list(g["psfs"])
+    psfs = golden_io.kernels(g, "psfs")            # each view's kernel in its own dims
     k1, k2 = ref.prepare_kernels(psfs, pt, T)
-    np.testing.assert_array_equal(np.stack(k1), g["k1"])
-    np.testing.assert_allclose(np.stack(k2), g["k2"], rtol=1e-6, atol=1e-12)
+    for v in range(len(psfs)):
+        assert k1[v].shape == k2[v].shape == psfs[v].shape
+        np.testing.assert_array_equal(k1[v], golden_io.kernels(g, "k1")[v])
+        np.testing.assert_allclose(k2[v], golden_io.kernels(g, "k2")[v], rtol=1e-6, atol=1e-12)
     res = ref.mv_deconvolution(list(g["imgs"]), list(g["weights"]), psfs, pt, int(g["iters"]),
                                float(g["lam"]), ij_threads=T)
     assert rel_l2(res.psi, g["psi"]) < 1e-6
