@@ -336,7 +336,19 @@ int spim_dog_interest_points(const float* img, const int64_t* dims, const spim_d
                              float* dog_out, spim_interest_point* out, int64_t max_out,
                              int64_t* nout);
 
-/* The two DoG calls above keep a per-device workspace between calls (the
+/* The same two calls with the reference's choice of GPU mode (DifferenceOfGaussian.java:44,
+ * 338-340), i.e. how the Gaussians see beyond the image: `extension` is one of the two
+ * values below, anything else returns SPIMDECON_ERR_ARG.  Contract otherwise as above (host
+ * or device pointers, the capacity rule, the workspace); the calls without _ext are these
+ * with SPIM_DOG_EXTEND_MIRROR.  (spim_dog_params keeps its size: callers pass it by pointer.) */
+#define SPIM_DOG_EXTEND_MIRROR 0   /* accurate: extendMirrorSingle (DifferenceOfGaussianCUDA.java:153-154) */
+#define SPIM_DOG_EXTEND_BORDER 1   /* approximate: EXTEND_BORDER_PIXELS (:125-148)                          */
+int spim_dog_compute_ext(const float* img, const int64_t* dims, const spim_dog_params* p, int32_t extension,
+                         float* dog_out, spim_peak* peaks, int64_t max_peaks, int64_t* npeaks);
+int spim_dog_interest_points_ext(const float* img, const int64_t* dims, const spim_dog_params* p, int32_t extension,
+                                 float* dog_out, spim_interest_point* out, int64_t max_out, int64_t* nout);
+
+/* The DoG calls above keep a per-device workspace between calls (the
  * intermediate Gaussians, candidate lists; ~12 B per voxel of the largest view seen)
  * instead of allocating per call; this frees it.  No reference counterpart (the
  * reference's CUDA library allocates per call, CUDASeparableConvolution.java:13-21). */

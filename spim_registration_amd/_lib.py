@@ -138,6 +138,10 @@ SIGNATURES = {
                                    _i64, _pi64]),
     "spim_dog_interest_points": (C.c_int, [_pf, _pi64, C.POINTER(DogParams), _pf,
                                            C.POINTER(InterestPointC), _i64, _pi64]),
+    "spim_dog_compute_ext": (C.c_int, [_pf, _pi64, C.POINTER(DogParams), _i32, _pf, C.POINTER(Peak),
+                                       _i64, _pi64]),
+    "spim_dog_interest_points_ext": (C.c_int, [_pf, _pi64, C.POINTER(DogParams), _i32, _pf,
+                                               C.POINTER(InterestPointC), _i64, _pi64]),
     "spim_dog_release_workspace": (C.c_int, [C.c_int]),
     "spim_psf_release_workspace": (C.c_int, [C.c_int]),
     "spim_save_interest_points": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(InterestPointC),

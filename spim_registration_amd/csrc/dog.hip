@@ -5,7 +5,10 @@
 //   spim/process/cuda/CUDASeparableConvolution.java:13-21        convolve_N ABI
 //   spim/process/cuda/CUDASeparableConvolutionFunctions.java:127-245 kernels, sizes
 //   spim/process/interestpointdetection/ProcessDOG.java:40-178   pipeline, sigmas
-//   spim/process/interestpointdetection/DifferenceOfGaussianCUDA.java:116-181 (accurate = mirror-single)
+//   spim/process/interestpointdetection/DifferenceOfGaussianCUDA.java:116-181  both GPU modes:
+//       accurate    = extendMirrorSingle (:153-154)                  -> OOB_MIRROR
+//       approximate = EXTEND_BORDER_PIXELS on the plain image (:125-148, blocks of
+//                     BlockGeneratorVariableSizeSimple, which do not change a voxel) -> OOB_BORDER
 //   spim/process/interestpointdetection/DifferenceOfGaussianNewPeakFinder.java:54-136
 //   mpicbg/spim/segmentation/InteractiveIntegral.java:360-468     findPeaks / isSpecialPoint
 //   spim/process/fusion/FusionHelper.java:176-234                 normalizeImage
@@ -380,6 +383,8 @@ __device__ __forceinline__ int mirror32(int i, int n) {
     bool o;
     return ext_index32(i, n, OOB_MIRROR, o);
 }
+// EXTEND_BORDER_PIXELS: the nearest voxel of the axis
+__device__ __forceinline__ int clamp32(int i, int n) { return min(max(i, 0), n - 1); }
 
 // LDS writes visible to the block, without the release fence of __syncthreads (which
 // would also wait for the planes loaded ahead)
@@ -441,10 +446,18 @@ __device__ __forceinline__ DzBox xcd_box(bool xcd) {
 // a second item, and the blocks of a CU run their phases in step, so the SIMDs of those
 // waves set the pace: no gain at 48), 4 blocks per CU; 768^3: k_dog_xy 1.63 -> 1.47 ms,
 // DoG 3.67 -> 3.52 ms (profiles/r05_dog_strips_ab.txt).
-template <int KW, int TY, bool BUF = true, int JT = 0>
+// BORDER (the fused kernels' only two modes): false = mirror-single, true = clamp to the
+// edge voxel (EXTEND_BORDER_PIXELS).  It is read only where a step that is not `inside`
+// forms a source index.  The carried rows stay valid under clamp: the x results of row
+// clamp(y) ARE the x results of that row of the extended image.  (A template parameter: as
+// a runtime argument it cost the 15-tap kernel, at its 128-VGPR bound, 4 spilled VGPRs and
+// changed the registers of the z kernels -- DESIGN.md 4.2; the mirror instantiations are
+// the code they were.)
+template <int KW, int TY, bool BUF = true, int JT = 0, bool BORDER = false>
 __global__ __launch_bounds__(256, 4) void k_dog_xy(Dims3 d, const float* __restrict__ in, const float2* __restrict__ kx,
                                                 const float2* __restrict__ ky, float2* __restrict__ g12,
                                                 const float* __restrict__ mm, int xcd, int mm_exact) {
+    constexpr bool border = BORDER;
     constexpr int R = KW / 2;
     constexpr int IW = kDxyTX + KW - 1;          // staged input columns
     constexpr int IP = dxy_in_pitch(IW);         // pitch (see dxy_in_pitch)
@@ -481,6 +494,8 @@ __global__ __launch_bounds__(256, 4) void k_dog_xy(Dims3 d, const float* __restr
     // finite (mm[2] == 0) and the image is normalised by its own range, every staged value
     // lies in [0, 1] and every partial sum is finite and never -0 (it starts at +0; the
     // taps are >= 0), so such a tap's +-0 product leaves the sum's bits unchanged: skipped.
+    // (Either extension: a clamped index stages an image value like a mirrored one, so the
+    // [0, 1] range and the argument hold for the border mode too -- the trim is kept there.)
     // Otherwise (NaN / inf in the image, a caller-given range) every padded tap is applied,
     // as before (one uniform branch per item between the two unrolled tap loops).
     const bool trim = JT > 0 && mm && norm && mm_exact != 0 && mm[2] == 0.0f;
@@ -522,11 +537,14 @@ __global__ __launch_bounds__(256, 4) void k_dog_xy(Dims3 d, const float* __restr
                 for (int e = 0; e < NEc; ++e) v[e] = in[base + uint32_t(min(r0 + RPT * e, NR - 1)) * uint32_t(nx)];
             }
         } else {
-            const uint32_t gxo = plane + uint32_t(mirror32(x0 - R + min(col, IW - 1), nx));
+            const int xx = x0 - R + min(col, IW - 1);
+            const uint32_t gxo = plane + uint32_t(border ? clamp32(xx, nx) : mirror32(xx, nx));
 #pragma unroll
             for (int e = 0; e < NEc; ++e) {
                 const int yy = ys + min(r0 + RPT * e, NR - 1);
-                const int my = yrefl ? (ny - 1) - abs((ny - 1) - abs(yy)) : mirror32(yy, ny);
+                const int my = border  ? clamp32(yy, ny)
+                               : yrefl ? (ny - 1) - abs((ny - 1) - abs(yy))
+                                       : mirror32(yy, ny);
                 if constexpr (BUF)
                     v[e] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                                          rin, int((gxo + uint32_t(my) * uint32_t(nx)) * 4u), 0, 0));
@@ -832,15 +850,18 @@ __device__ __forceinline__ float dz_max3(float a, float b, float c) {
 // SL: the source plane of each load from scalar mirror arithmetic (needs nz > KW / 2: one
 // reflection) and a buffer resource per plane, so the load's address is the column's
 // constant byte offset; else the LDS plane table and a 64-bit address per load.
+// BORDER: the plane index is clamped instead (either form; the host keeps the same
+// dispatch conditions for both modes, under clamp they are merely conservative).
 // FROMDOG: the split z stage's test pass -- the DoG planes are read from the image
 // k_dog_zconv stored (`dsrc`, PD planes ahead) instead of being convolved here; the test,
 // the ring and the candidate records are the same code, so the same candidates.
-template <int KW, int BY, int PD, int BX, bool ONE, bool SL, bool FROMDOG = false>
+template <int KW, int BY, int PD, int BX, bool ONE, bool SL, bool FROMDOG = false, bool BORDER = false>
 __global__ __launch_bounds__(BX * BY) void k_dog_z(Dims3 d, const float2* __restrict__ g12,
                                                          const float2* __restrict__ kz, float scale, int zc_len,
                                                          float* __restrict__ dog, float minv, int want,
                                                          const PeakSink* __restrict__ sink, int xcd,
                                                          const float* __restrict__ dsrc = nullptr) {
+    constexpr bool border = BORDER;
     constexpr int R = KW / 2;
     constexpr int NW = FROMDOG ? 12 : KW + PD;
     static_assert(NW % 4 == 0, "ring slots are compile-time: the unrolled rotation is whole ring turns");
@@ -874,7 +895,8 @@ __global__ __launch_bounds__(BX * BY) void k_dog_z(Dims3 d, const float2* __rest
     __shared__ uint32_t zoff[SL || FROMDOG ? 1 : kDzMaxLen];
     if constexpr (!SL && !FROMDOG)
         for (int i = t; i < kDzMaxLen; i += BX * BY)
-            zoff[i] = uint32_t(mirror32(qa - R + min(i, len - 1), nz)) * pstride;
+            zoff[i] = uint32_t(border ? clamp32(qa - R + min(i, len - 1), nz)
+                                      : mirror32(qa - R + min(i, len - 1), nz)) * pstride;
     if (t < 4) nanq[t] = INT_MIN;   // (no plane)
     __syncthreads();
     // unconditional loads (columns outside the volume read column 0): no branch merge,
@@ -891,7 +913,8 @@ __global__ __launch_bounds__(BX * BY) void k_dog_z(Dims3 d, const float2* __rest
     auto ld = [&](int i) -> float2 {
         if constexpr (SL) {
             const int tz = qa - R + min(i, len - 1);
-            const int m = (nz - 1) - abs((nz - 1) - abs(tz));   // mirror-single, one reflection
+            // mirror-single, one reflection; or the clamped plane
+            const int m = border ? clamp32(tz, nz) : (nz - 1) - abs((nz - 1) - abs(tz));
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<float2*>(g12) + size_t(uint32_t(m)) * pstride, 0, int(plane_bytes), 0x00020000);
             return __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rs, int(col * 8u), 0, 0));
@@ -1016,10 +1039,11 @@ __global__ __launch_bounds__(BX * BY) void k_dog_z(Dims3 d, const float2* __rest
 // Same tap order and DoG expression as k_dog_z: the same bits.
 // (plane bytes nx * ny * 8 < 2^31: one buffer resource per source plane; ONE: the DoG
 // image below 2 GiB, one resource with the plane in the scalar offset)
-template <int KW, int PD, bool ONE, bool ONEG>
+template <int KW, int PD, bool ONE, bool ONEG, bool BORDER = false>
 __global__ __launch_bounds__(256) void k_dog_zconv(Dims3 d, const float2* __restrict__ g12,
                                                    const float2* __restrict__ kz, float scale, int zc_len,
                                                    float* __restrict__ dog) {
+    constexpr bool border = BORDER;
     constexpr int R = KW / 2;
     constexpr int NW = KW + PD;
     const int nx = int(d.nx), ny = int(d.ny), nz = int(d.nz);
@@ -1040,9 +1064,10 @@ __global__ __launch_bounds__(256) void k_dog_zconv(Dims3 d, const float2* __rest
     const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float2*>(g12), 0, int(uint32_t(g12_bytes < 0xffffffffull ? g12_bytes : 0xffffffffull)), 0x00020000);
     auto ld = [&](int i) -> float2 {
-        // mirror-single extension, one reflection (the host takes this kernel for nz > KW / 2)
+        // mirror-single extension, one reflection (the host takes this kernel for nz > KW / 2),
+        // or (border) the clamped plane
         const int tz = z0 - R + min(i, len - 1);
-        const int m = (nz - 1) - abs((nz - 1) - abs(tz));
+        const int m = border ? clamp32(tz, nz) : (nz - 1) - abs((nz - 1) - abs(tz));
         if constexpr (ONEG)
             return __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(rg, int(col * 8u),
                                                                                    int(uint32_t(m) * pstride * 8u), 0));
@@ -1704,9 +1729,12 @@ int bits_for(uint64_t v) {
     return b;
 }
 
-void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, float* dog_out, bool need_dog,
+// oob: OOB_MIRROR (the reference's accurate mode) or OOB_BORDER (its approximate mode)
+void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, int oob, float* dog_out, bool need_dog,
              hipStream_t s, DogWork& w, DogRun& r) {
     SD_CHECK(img && dims && p, SPIMDECON_ERR_ARG, "null argument");
+    SD_CHECK(oob == OOB_MIRROR || oob == OOB_BORDER, SPIMDECON_ERR_STATE, "bad extension mode");
+    const bool border = oob == OOB_BORDER;
     SD_CHECK(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, SPIMDECON_ERR_ARG, "bad dims");
     SD_CHECK(p->localization == 0 || p->localization == 1, SPIMDECON_ERR_ARG,
              "localization must be 0 (none) or 1 (quadratic); the Gaussian fit is not implemented in "
@@ -1839,23 +1867,27 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, fl
         // (k_minmax's own range: the per-value range check is skipped; SPIMDECON_DOG_MM_EXACT=0
         // keeps it -- 1.52-1.62 vs 1.66 ms per 768^3, bit-exact, gpu_r3z11.sh)
         const int mmx = !use_given && dog_env("SPIMDECON_DOG_MM_EXACT", 1) != 0 ? 1 : 0;
-#define SD_DOGXY3(KV, JV)                                                                                   \
-        if (xbuf) hipLaunchKernelGGL((k_dog_xy<KV, ty, true, JV>), gxy, dim3(256), 0, s, d, in, kp2(0), kp2(1), w.g12.p, w.mm.p, xcd_xy, mmx); \
-        else hipLaunchKernelGGL((k_dog_xy<KV, ty, false, JV>), gxy, dim3(256), 0, s, d, in, kp2(0), kp2(1), w.g12.p, w.mm.p, xcd_xy, mmx);
+#define SD_DOGXY4(KV, JV, BV)                                                                               \
+        if (xbuf) hipLaunchKernelGGL((k_dog_xy<KV, ty, true, JV, BV>), gxy, dim3(256), 0, s, d, in, kp2(0), kp2(1), w.g12.p, w.mm.p, xcd_xy, mmx); \
+        else hipLaunchKernelGGL((k_dog_xy<KV, ty, false, JV, BV>), gxy, dim3(256), 0, s, d, in, kp2(0), kp2(1), w.g12.p, w.mm.p, xcd_xy, mmx);
+#define SD_DOGXY3(KV, JV) if (border) { SD_DOGXY4(KV, JV, true) } else { SD_DOGXY4(KV, JV, false) }
 #define SD_DOGXY(KV) if (jt == 1) { SD_DOGXY3(KV, 1) } else { SD_DOGXY3(KV, 0) }
         if (K == 7) { SD_DOGXY(7) } else if (K == 15) { SD_DOGXY(15) } else { SD_DOGXY(31) }
 #undef SD_DOGXY
 #undef SD_DOGXY3
+#undef SD_DOGXY4
         SD_HIP(hipGetLastError());
         if (split) {
             const int64_t waves = ceil_div(d.nx, int64_t(64)) * d.ny;
             const dim3 gc(unsigned(ceil_div(waves, int64_t(4))), unsigned(ceil_div(d.nz, int64_t(zc1))));
             const bool one1 = uint64_t(n) * 4u < 0x80000000ull, oneg = uint64_t(n) * 8u < 0xffffffffull;
-#define SD_DOGZC(KV) if (one1 && oneg) hipLaunchKernelGGL((k_dog_zconv<KV, kDzcPD, true, true>), gc, dim3(256), 0, s, d, w.g12.p, kp2(2), kinv, zc1, dogp); \
-            else if (oneg) hipLaunchKernelGGL((k_dog_zconv<KV, kDzcPD, false, true>), gc, dim3(256), 0, s, d, w.g12.p, kp2(2), kinv, zc1, dogp); \
-            else hipLaunchKernelGGL((k_dog_zconv<KV, kDzcPD, false, false>), gc, dim3(256), 0, s, d, w.g12.p, kp2(2), kinv, zc1, dogp);
+#define SD_DOGZC2(KV, BV) if (one1 && oneg) hipLaunchKernelGGL((k_dog_zconv<KV, kDzcPD, true, true, BV>), gc, dim3(256), 0, s, d, w.g12.p, kp2(2), kinv, zc1, dogp); \
+            else if (oneg) hipLaunchKernelGGL((k_dog_zconv<KV, kDzcPD, false, true, BV>), gc, dim3(256), 0, s, d, w.g12.p, kp2(2), kinv, zc1, dogp); \
+            else hipLaunchKernelGGL((k_dog_zconv<KV, kDzcPD, false, false, BV>), gc, dim3(256), 0, s, d, w.g12.p, kp2(2), kinv, zc1, dogp);
+#define SD_DOGZC(KV) if (border) { SD_DOGZC2(KV, true) } else { SD_DOGZC2(KV, false) }
             if (K == 7) { SD_DOGZC(7) } else if (K == 15) { SD_DOGZC(15) } else { SD_DOGZC(31) }
 #undef SD_DOGZC
+#undef SD_DOGZC2
             SD_HIP(hipGetLastError());
         }
     } else {
@@ -1868,10 +1900,10 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, fl
             grow(w.dog, size_t(n));
             dogp = w.dog.p;
         }
-        sep_pass(d, 0, in, in, kp(0, 0), kp(0, 1), K, OOB_MIRROR, 0.f, w.tmp_a.p, w.tmp_b.p, false, 0.f, w.mm.p, s);
-        sep_pass(d, 1, w.tmp_a.p, w.tmp_b.p, kp(1, 0), kp(1, 1), K, OOB_MIRROR, 0.f, w.tmp_c.p, w.tmp_d.p, false,
+        sep_pass(d, 0, in, in, kp(0, 0), kp(0, 1), K, oob, 0.f, w.tmp_a.p, w.tmp_b.p, false, 0.f, w.mm.p, s);
+        sep_pass(d, 1, w.tmp_a.p, w.tmp_b.p, kp(1, 0), kp(1, 1), K, oob, 0.f, w.tmp_c.p, w.tmp_d.p, false,
                  0.f, nullptr, s);
-        sep_pass(d, 2, w.tmp_c.p, w.tmp_d.p, kp(2, 0), kp(2, 1), K, OOB_MIRROR, 0.f, dogp, nullptr, true, kinv,
+        sep_pass(d, 2, w.tmp_c.p, w.tmp_d.p, kp(2, 0), kp(2, 1), K, oob, 0.f, dogp, nullptr, true, kinv,
                  nullptr, s);
     }
     unsigned total = 0;
@@ -1899,8 +1931,8 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, fl
             SD_HIP(hipMemcpyAsync(w.sink.p, &pk, sizeof(pk), hipMemcpyHostToDevice, s));   // (synchronised below)
             const bool one = uint64_t(n) * 4u < 0x80000000ull;
             const int want = wmin | (wmax << 1);
-#define SD_DOGZ4(KV, BYV, ONEV, SLV) hipLaunchKernelGGL((k_dog_z<KV, BYV, kDzPD, 64, ONEV, SLV>), gz, dim3(64 * BYV), 0, s, d, w.g12.p, kp2(2), kinv, zc, dst, min_peak, want, w.sink.p, xcd);
-#define SD_DOGZ3(KV, ONEV, SLV) SD_DOGZ4(KV, bz_y, ONEV, SLV)
+#define SD_DOGZ4(KV, BYV, ONEV, SLV, BV) hipLaunchKernelGGL((k_dog_z<KV, BYV, kDzPD, 64, ONEV, SLV, false, BV>), gz, dim3(64 * BYV), 0, s, d, w.g12.p, kp2(2), kinv, zc, dst, min_peak, want, w.sink.p, xcd);
+#define SD_DOGZ3(KV, ONEV, SLV) if (border) { SD_DOGZ4(KV, bz_y, ONEV, SLV, true) } else { SD_DOGZ4(KV, bz_y, ONEV, SLV, false) }
 #define SD_DOGZ2(KV, ONEV) if (zsl) { SD_DOGZ3(KV, ONEV, true) } else { SD_DOGZ3(KV, ONEV, false) }
 #define SD_DOGZ(KV) if (one) { SD_DOGZ2(KV, true) } else { SD_DOGZ2(KV, false) }
             if (K == 7) { SD_DOGZ(7) } else if (K == 15) { SD_DOGZ(15) } else { SD_DOGZ(31) }
@@ -1944,16 +1976,24 @@ struct StreamHolder {   // the workspace's stream (held under its mutex)
 
 // DifferenceOfGaussianNewPeakFinder.getSimplePeaks level: candidates with
 // |v| >= threshold (localization 0) or threshold / 10 (localization 1)
-void dog_compute(const float* img, const int64_t* dims, const spim_dog_params* p, float* dog_out,
+// SPIM_DOG_EXTEND_* (the C ABI's `extension` argument) -> the kernels' mode
+int dog_oob(int32_t extension) {
+    SD_CHECK(extension == SPIM_DOG_EXTEND_MIRROR || extension == SPIM_DOG_EXTEND_BORDER, SPIMDECON_ERR_ARG,
+             "extension must be SPIM_DOG_EXTEND_MIRROR (0) or SPIM_DOG_EXTEND_BORDER (1)");
+    return extension == SPIM_DOG_EXTEND_BORDER ? OOB_BORDER : OOB_MIRROR;
+}
+
+void dog_compute(const float* img, const int64_t* dims, const spim_dog_params* p, int32_t extension, float* dog_out,
                  spim_peak* peaks, int64_t max_peaks, int64_t* npeaks) {
     SD_CHECK(npeaks && p, SPIMDECON_ERR_ARG, "null argument");
+    const int oob = dog_oob(extension);
     check_device(p->device);
     DeviceGuard guard(p->device);
     DogWork& w = dog_work(p->device);
     std::lock_guard<std::mutex> lk(w.mu);
     StreamHolder sh(w);
     DogRun r;
-    dog_run(img, dims, p, dog_out, dog_out != nullptr, sh.s, w, r);
+    dog_run(img, dims, p, oob, dog_out, dog_out != nullptr, sh.s, w, r);
     *npeaks = r.np;
     const int64_t m = peaks ? std::min(r.np, max_peaks) : 0;
     std::vector<PeakOut> hp(std::max<int64_t>(m, 0));
@@ -1996,16 +2036,17 @@ __global__ void k_to_points(const PeakOut* __restrict__ pk, const LocOut* __rest
 // ProcessDOG.compute's result: interest points after Localization (:150-168).  The
 // candidates (threshold / 10 with quadratic localisation: millions on a noisy 768^3
 // view) stay on the device; only the interest points are copied out.
-void dog_interest_points(const float* img, const int64_t* dims, const spim_dog_params* p, float* dog_out,
-                         spim_interest_point* out, int64_t max_out, int64_t* nout) {
+void dog_interest_points(const float* img, const int64_t* dims, const spim_dog_params* p, int32_t extension,
+                         float* dog_out, spim_interest_point* out, int64_t max_out, int64_t* nout) {
     SD_CHECK(nout && p, SPIMDECON_ERR_ARG, "null argument");
+    const int oob = dog_oob(extension);
     check_device(p->device);
     DeviceGuard guard(p->device);
     DogWork& w = dog_work(p->device);
     std::lock_guard<std::mutex> lk(w.mu);
     StreamHolder sh(w);
     DogRun r;
-    dog_run(img, dims, p, dog_out, p->localization == 1 || dog_out != nullptr, sh.s, w, r);
+    dog_run(img, dims, p, oob, dog_out, p->localization == 1 || dog_out != nullptr, sh.s, w, r);
     const int64_t np = r.np;
     int64_t n = 0;
     const spim_interest_point* res = nullptr;
@@ -2095,7 +2136,13 @@ extern "C" void spim_dog_params_default(spim_dog_params* p) {
 extern "C" int spim_dog_interest_points(const float* img, const int64_t* dims, const spim_dog_params* p,
                                         float* dog_out, spim_interest_point* out, int64_t max_out,
                                         int64_t* nout) {
-    return guarded([&] { dog_interest_points(img, dims, p, dog_out, out, max_out, nout); });
+    return spim_dog_interest_points_ext(img, dims, p, SPIM_DOG_EXTEND_MIRROR, dog_out, out, max_out, nout);
+}
+
+extern "C" int spim_dog_interest_points_ext(const float* img, const int64_t* dims, const spim_dog_params* p,
+                                            int32_t extension, float* dog_out, spim_interest_point* out,
+                                            int64_t max_out, int64_t* nout) {
+    return guarded([&] { dog_interest_points(img, dims, p, extension, dog_out, out, max_out, nout); });
 }
 
 extern "C" int spim_dog_release_workspace(int device) {
@@ -2105,5 +2152,11 @@ extern "C" int spim_dog_release_workspace(int device) {
 extern "C" int spim_dog_compute(const float* img, const int64_t* dims, const spim_dog_params* p,
                                 float* dog_out, spim_peak* peaks, int64_t max_peaks,
                                 int64_t* npeaks) {
-    return guarded([&] { dog_compute(img, dims, p, dog_out, peaks, max_peaks, npeaks); });
+    return spim_dog_compute_ext(img, dims, p, SPIM_DOG_EXTEND_MIRROR, dog_out, peaks, max_peaks, npeaks);
+}
+
+extern "C" int spim_dog_compute_ext(const float* img, const int64_t* dims, const spim_dog_params* p,
+                                    int32_t extension, float* dog_out, spim_peak* peaks, int64_t max_peaks,
+                                    int64_t* npeaks) {
+    return guarded([&] { dog_compute(img, dims, p, extension, dog_out, peaks, max_peaks, npeaks); });
 }

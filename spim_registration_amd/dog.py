@@ -25,17 +25,33 @@ class InterestPoint:
     intensity: float | None = None
 
 
+# the reference's two GPU modes (DifferenceOfGaussian.java:44,338-340) -> SPIM_DOG_EXTEND_*
+EXTENSIONS = {"mirror": 0, "border": 1}
+
+
+def _extension(extension) -> int:
+    """'mirror' (accurate: extendMirrorSingle) or 'border' (approximate:
+    EXTEND_BORDER_PIXELS) -> the C ABI's code; anything else raises."""
+    try:
+        return EXTENSIONS[extension]
+    except (KeyError, TypeError):
+        raise ValueError(f"extension must be 'mirror' or 'border', not {extension!r}") from None
+
+
 def compute(img: np.ndarray, sigma: float = 1.8, threshold: float = 0.008, localization: int = 0,
             image_sigma=(0.5, 0.5, 0.5), find_min: bool = False, find_max: bool = True,
             min_intensity: float = float("nan"), max_intensity: float = float("nan"),
             keep_intensity: bool = False, device: int | None = None, ij_threads: int = 8,
-            return_dog: bool = False, max_peaks: int | None = None):
+            return_dog: bool = False, max_peaks: int | None = None, extension: str = "mirror"):
     """ProcessDOG.compute: returns the list of InterestPoint (and the DoG image
     when ``return_dog``).  ``img`` is a [z, y, x] float32 volume (not modified):
     a numpy array, or a torch tensor on the GPU -- a view already resident in HBM
     is read in place (the returned DoG image is then a torch tensor too).
     ``device``: the GPU that runs the pass; default the tensor's own GPU (device 0 for
-    a host array)."""
+    a host array).  ``extension``: how the Gaussians see beyond the image -- 'mirror'
+    (the reference's accurate GPU mode) or 'border' (its approximate one: the edge voxel
+    repeated, DifferenceOfGaussianCUDA.java:125-148)."""
+    ext = _extension(extension)
     lib = _lib.load()
     on_dev = hasattr(img, "is_cuda") and img.is_cuda
     if device is None:
@@ -46,7 +62,7 @@ def compute(img: np.ndarray, sigma: float = 1.8, threshold: float = 0.008, local
             raise ValueError("img must be 3D [z, y, x]")
         return _compute_device(lib, img, sigma, threshold, localization, image_sigma, find_min, find_max,
                                min_intensity, max_intensity, keep_intensity, device, ij_threads, return_dog,
-                               max_peaks)
+                               max_peaks, ext)
     img = np.ascontiguousarray(img, np.float32)
     if img.ndim != 3:
         raise ValueError("img must be 3D [z, y, x]")
@@ -69,11 +85,11 @@ def compute(img: np.ndarray, sigma: float = 1.8, threshold: float = 0.008, local
     pts = (_lib.InterestPointC * cap)()
     n = C.c_int64(0)
     dptr = fptr(dog) if dog is not None else None
-    check(lib.spim_dog_interest_points(fptr(img), dims, C.byref(p), dptr, pts, cap, C.byref(n)))
+    check(lib.spim_dog_interest_points_ext(fptr(img), dims, C.byref(p), ext, dptr, pts, cap, C.byref(n)))
     total = int(n.value)
     if total > cap:   # rerun with the exact capacity
         pts = (_lib.InterestPointC * total)()
-        check(lib.spim_dog_interest_points(fptr(img), dims, C.byref(p), dptr, pts, total, C.byref(n)))
+        check(lib.spim_dog_interest_points_ext(fptr(img), dims, C.byref(p), ext, dptr, pts, total, C.byref(n)))
     out = []
     for i in range(min(total, len(pts))):
         ip = pts[i]
@@ -99,8 +115,8 @@ def _params(lib, sigma, threshold, localization, image_sigma, find_min, find_max
 IP_DTYPE = np.dtype([("pos", "<f8", (3,)), ("intensity", "<f4"), ("is_max", "<i4")])
 
 
-def _points_device(lib, img, p, dog):
-    """spim_dog_interest_points on a GPU tensor: a numpy IP_DTYPE record array."""
+def _points_device(lib, img, p, dog, ext=0):
+    """spim_dog_interest_points_ext on a GPU tensor: a numpy IP_DTYPE record array."""
     import torch
     torch.cuda.synchronize(img.device)   # the library runs on its own stream
     dims = (C.c_int64 * 3)(img.shape[2], img.shape[1], img.shape[0])
@@ -111,20 +127,21 @@ def _points_device(lib, img, p, dog):
     n = C.c_int64(0)
     while True:
         buf = np.empty(cap, IP_DTYPE)
-        check(lib.spim_dog_interest_points(iptr, dims, C.byref(p), dptr,
-                                           buf.ctypes.data_as(C.POINTER(_lib.InterestPointC)), cap, C.byref(n)))
+        check(lib.spim_dog_interest_points_ext(iptr, dims, C.byref(p), ext, dptr,
+                                               buf.ctypes.data_as(C.POINTER(_lib.InterestPointC)), cap,
+                                               C.byref(n)))
         if int(n.value) <= cap:
             return buf[:int(n.value)]
         cap = int(n.value)
 
 
 def _compute_device(lib, img, sigma, threshold, localization, image_sigma, find_min, find_max, min_intensity,
-                    max_intensity, keep_intensity, device, ij_threads, return_dog, max_peaks):
+                    max_intensity, keep_intensity, device, ij_threads, return_dog, max_peaks, ext=0):
     import torch
     p = _params(lib, sigma, threshold, localization, image_sigma, find_min, find_max, min_intensity,
                 max_intensity, device, ij_threads)
     dog = torch.empty_like(img) if return_dog else None
-    rec = _points_device(lib, img, p, dog)
+    rec = _points_device(lib, img, p, dog, ext)
     if max_peaks is not None:
         rec = rec[:int(max_peaks)]
     out = [InterestPoint(i, tuple(r["pos"].tolist()), float(r["intensity"]) if keep_intensity else None)
@@ -135,26 +152,28 @@ def _compute_device(lib, img, sigma, threshold, localization, image_sigma, find_
 def interest_points_array(img, sigma: float = 1.8, threshold: float = 0.008, localization: int = 0,
                           image_sigma=(0.5, 0.5, 0.5), find_min: bool = False, find_max: bool = True,
                           min_intensity: float = float("nan"), max_intensity: float = float("nan"),
-                          device: int | None = None, ij_threads: int = 8):
+                          device: int | None = None, ij_threads: int = 8, extension: str = "mirror"):
     """ProcessDOG.compute on a GPU tensor, as arrays: (positions (n, 3) x, y, z;
     intensities (n,)) in the reference's order -- no per-point Python objects.
-    ``device`` defaults to the tensor's own GPU."""
+    ``device`` defaults to the tensor's own GPU; ``extension`` as in ``compute``."""
+    ext = _extension(extension)
     lib = _lib.load()
     if device is None:
         device = img.device.index
     img = img.contiguous().float()
     p = _params(lib, sigma, threshold, localization, image_sigma, find_min, find_max, min_intensity,
                 max_intensity, device, ij_threads)
-    rec = _points_device(lib, img, p, None)
+    rec = _points_device(lib, img, p, None, ext)
     return np.ascontiguousarray(rec["pos"]), np.ascontiguousarray(rec["intensity"])
 
 
 def simple_peaks(img: np.ndarray, sigma: float = 1.8, threshold: float = 0.008, localization: int = 0,
                  image_sigma=(0.5, 0.5, 0.5), find_min: bool = False, find_max: bool = True,
                  min_intensity: float = float("nan"), max_intensity: float = float("nan"),
-                 device: int = 0, ij_threads: int = 8):
+                 device: int = 0, ij_threads: int = 8, extension: str = "mirror"):
     """DifferenceOfGaussianNewPeakFinder.getSimplePeaks: [(x, y, z, |v|, is_min, is_max)]
-    (threshold / 10 when ``localization`` is 1)."""
+    (threshold / 10 when ``localization`` is 1); ``extension`` as in ``compute``."""
+    ext = _extension(extension)
     lib = _lib.load()
     img = np.ascontiguousarray(img, np.float32)
     p = _lib.DogParams()
@@ -167,9 +186,9 @@ def simple_peaks(img: np.ndarray, sigma: float = 1.8, threshold: float = 0.008, 
     p.ij_threads, p.device = int(ij_threads), int(device)
     dims = (C.c_int64 * 3)(img.shape[2], img.shape[1], img.shape[0])
     n = C.c_int64(0)
-    check(lib.spim_dog_compute(fptr(img), dims, C.byref(p), None, None, 0, C.byref(n)))
+    check(lib.spim_dog_compute_ext(fptr(img), dims, C.byref(p), ext, None, None, 0, C.byref(n)))
     pk = (_lib.Peak * max(int(n.value), 1))()
-    check(lib.spim_dog_compute(fptr(img), dims, C.byref(p), None, pk, int(n.value), C.byref(n)))
+    check(lib.spim_dog_compute_ext(fptr(img), dims, C.byref(p), ext, None, pk, int(n.value), C.byref(n)))
     return [(q.x, q.y, q.z, q.intensity, bool(q.is_min), bool(q.is_max)) for q in pk[:int(n.value)]]
 
 

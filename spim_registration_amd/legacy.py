@@ -7,9 +7,12 @@ Paths under /root/reference/src/main/java/spim/process/cuda/:
   CUDASeparableConvolution          CUDASeparableConvolution.java:9-21
   CUDASeparableConvolutionFunctions CUDASeparableConvolutionFunctions.java:127-245
   BlockGeneratorFixedSizePrecise    BlockGeneratorFixedSizePrecise.java:25-101
+  BlockGeneratorVariableSizeSimple  BlockGeneratorVariableSizeSimple.java:30-132
+  BlockGeneratorVariableSizePrecise BlockGeneratorVariableSizePrecise.java:30-79
   Block (copy/paste)                Block.java:67-359
 
-plus the per-block driver of spim/process/fusion/deconvolution/MVDeconFFTThreads.java:52-94.
+plus the per-block drivers of spim/process/fusion/deconvolution/MVDeconFFTThreads.java:52-94 and
+spim/process/interestpointdetection/DifferenceOfGaussianCUDA.java:125-177.
 These are the call sites a Java maintainer keeps when swapping in
 libspimdecon.so as the JNA library; all arithmetic runs on the
 GPU inside the library.
@@ -200,10 +203,19 @@ class Block:
 
     def copy_block(self, source: np.ndarray, ext: str) -> np.ndarray:
         """Block.copyBlock (:114-153) from the extended source ('mirror' =
-        extendMirrorSingle, 'one' = extendValue(1), 'zero')."""
+        extendMirrorSingle, 'one' = extendValue(1), 'zero'); 'none' = the plain image,
+        where a block reaching outside it raises (the Java's access would throw)."""
         bx, by, bz = self.block_size
         ox, oy, oz = self.offset
         nz, ny, nx = source.shape
+        if ext == "none":
+            if min(ox, oy, oz) < 0 or ox + bx > nx or oy + by > ny or oz + bz > nz:
+                raise ValueError(
+                    f"block offset {self.offset} size {self.block_size} reaches outside the unextended image "
+                    f"{(nx, ny, nz)}: the last block's effectiveOffset = currentBlock * effectiveSize "
+                    "(BlockGeneratorVariableSizeSimple.java:112) is off by the remainder when the block "
+                    "count does not divide the image size")
+            return np.array(source[oz:oz + bz, oy:oy + by, ox:ox + bx], np.float32, order="C")   # (a copy)
         zi, zin = _ext(np.arange(oz, oz + bz), nz, ext)
         yi, yin = _ext(np.arange(oy, oy + by), ny, ext)
         xi, xin = _ext(np.arange(ox, ox + bx), nx, ext)
@@ -255,6 +267,71 @@ class BlockGeneratorFixedSizePrecise:
         return blocks
 
 
+class BlockGeneratorVariableSizePrecise:
+    """BlockGeneratorVariableSizePrecise.java:30-79: every block carries the full halo
+    (the source is extended).  As in the reference (:58) the blocks before the last take
+    the remainder, so the offsets are exact only when the block counts divide the size."""
+
+    def __init__(self, num_blocks_dim):
+        self.num_blocks = tuple(int(b) for b in num_blocks_dim)
+
+    def divide_into_blocks(self, img_size, kernel_size):
+        n = len(img_size)
+        nb = self.num_blocks
+        blocks = []
+        for idx in np.ndindex(*reversed(nb)):   # LocalizingZeroMinIntervalIterator: dim 0 fastest
+            cur = list(reversed(idx))
+            es = [img_size[d] // nb[d] + (0 if cur[d] == nb[d] - 1 else img_size[d] % nb[d]) for d in range(n)]
+            if any(e <= 0 for e in es):
+                return None
+            eo = [cur[d] * es[d] for d in range(n)]
+            blocks.append(Block(tuple(es[d] + kernel_size[d] - 1 for d in range(n)),
+                                tuple(eo[d] - kernel_size[d] // 2 for d in range(n)), tuple(es), tuple(eo),
+                                tuple(kernel_size[d] // 2 for d in range(n))))
+        return blocks
+
+
+class BlockGeneratorVariableSizeSimple:
+    """BlockGeneratorVariableSizeSimple.java:30-132: ``num_blocks_dim`` blocks per
+    dimension whose edges inside the image carry a halo of ``kernel_size / 2`` voxels;
+    the image borders carry none (they are left to the native out-of-bounds strategy)."""
+
+    def __init__(self, num_blocks_dim):
+        self.num_blocks = tuple(int(b) for b in num_blocks_dim)
+
+    def divide_into_blocks(self, img_size, kernel_size):
+        n = len(img_size)
+        nb = self.num_blocks
+        blocks = []
+        for idx in np.ndindex(*reversed(nb)):   # LocalizingZeroMinIntervalIterator: dim 0 fastest
+            cur = list(reversed(idx))
+            bs, off, es, eo, lo = ([0] * n for _ in range(5))
+            for d in range(n):
+                if nb[d] == 1:                   # only one block (:88-92)
+                    bs[d] = es[d] = img_size[d]
+                elif cur[d] == 0:                # the first block (:93-98)
+                    es[d] = img_size[d] // nb[d]
+                    bs[d] = es[d] + kernel_size[d] // 2
+                elif cur[d] < nb[d] - 1:         # a block in the middle (:99-106)
+                    lo[d] = kernel_size[d] // 2
+                    es[d] = img_size[d] // nb[d]
+                    bs[d] = es[d] + kernel_size[d] - 1
+                    eo[d] = cur[d] * es[d]
+                    off[d] = eo[d] - kernel_size[d] // 2
+                else:                            # the last block (:107-114)
+                    lo[d] = kernel_size[d] // 2
+                    es[d] = img_size[d] // nb[d] + img_size[d] % nb[d]
+                    bs[d] = es[d] + kernel_size[d] // 2
+                    # (:112) the last block's own, larger size times its index: past the
+                    # true offset by (nb - 1) * remainder when nb does not divide the size
+                    eo[d] = cur[d] * es[d]
+                    off[d] = eo[d] - kernel_size[d] // 2
+                if es[d] <= 0:                   # (:116-120)
+                    return None
+            blocks.append(Block(tuple(bs), tuple(off), tuple(es), tuple(eo), tuple(lo)))
+        return blocks
+
+
 def cuda_coordinates(c):
     """MVDeconFFTThreads.getCUDACoordinates (:136-144): reverse the dims."""
     return list(reversed(list(c)))
@@ -278,5 +355,31 @@ def convolve_blocks_cuda(image: np.ndarray, kernel: np.ndarray, block_size, ext:
         blk = b.copy_block(image, ext)
         cuda.convolution3DfftCUDAInPlace(blk, cuda_coordinates(blk.shape[::-1]), kernel,
                                          cuda_coordinates(kernel.shape[::-1]), device)
+        b.paste_block(result, blk)
+    return result
+
+
+def gauss_blocks_cuda(image: np.ndarray, sigma_xyz, num_blocks_dim, accurate: bool,
+                      cuda: CUDASeparableConvolution, device: int) -> np.ndarray:
+    """DifferenceOfGaussianCUDA.process, the block loop (DifferenceOfGaussianCUDA.java:125-131,
+    151-177): blocks of ``num_blocks_dim`` (x, y, z) -> copy -> gauss with
+    EXTEND_BORDER_PIXELS -> paste.  ``accurate``: BlockGeneratorVariableSizePrecise over the
+    mirror-extended image; else BlockGeneratorVariableSizeSimple over the plain image (the
+    "approximate" mode; one block that is the whole image is the reference's single-block
+    branch, :132-148).  ``image`` is [z, y, x]; the kernel sizes are the unpadded Gaussian
+    lengths (getKernelSize, :189-195)."""
+    image = np.ascontiguousarray(image, np.float32)
+    nz, ny, nx = image.shape
+    sig = [float(s) for s in sigma_xyz]
+    ksize = [len(create_gaussian_kernel_1d(s, False)) for s in sig]
+    gen = (BlockGeneratorVariableSizePrecise if accurate else BlockGeneratorVariableSizeSimple)(num_blocks_dim)
+    blocks = gen.divide_into_blocks((nx, ny, nz), ksize)
+    if blocks is None:
+        raise ValueError("block smaller than kernel")
+    result = np.empty_like(image)
+    for b in blocks:
+        blk = b.copy_block(image, "mirror" if accurate else "none")
+        if not gauss(blk, blk.shape[::-1], sig, OutOfBounds.EXTEND_BORDER_PIXELS, 0.0, cuda, device):
+            raise RuntimeError("gauss failed (unsupported kernel size, or the native call returned false)")
         b.paste_block(result, blk)
     return result

@@ -104,9 +104,12 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
                       threshold: float = 0.008, localization: int = 1, radius: float = 2.0,
                       blending_border=(-8, -8, -8), blending_range=(12, 12, 12),
                       weight_type=input_prep.WeightType.VIRTUAL_WEIGHTS, device: int = 0,
-                      log=None, digest: bool = False, refine: str | None = None) -> TimepointResult:
+                      log=None, digest: bool = False, refine: str | None = None,
+                      dog_extension: str = "mirror") -> TimepointResult:
     """views: per view a [z, y, x] float32 torch tensor on the GPU (the acquired
-    stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z)."""
+    stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z);
+    dog_extension: the detect stage's 'mirror' (accurate) or 'border' (approximate) GPU
+    mode (``dog.compute``)."""
     import torch
     ms = {}
 
@@ -122,7 +125,7 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
     points = []
     for v in views:          # 1. ProcessDOG per view, read in place
         pos, _ = dog.interest_points_array(v, sigma=sigma, threshold=threshold, localization=localization,
-                                           device=device)
+                                           device=device, extension=dog_extension)
         points.append(pos)
     t = lap("detect", t)
     gres = None
