@@ -416,13 +416,17 @@ int spim_prepare_inputs(int nviews, const spim_view_source* views, const spim_in
  * 8. Weighted-average fusion --
  *    spim/process/fusion/weightedavg/ProcessParalellPortion(Weight).java:
  *    per fused voxel the (blending-weighted) mean of the views covering it.
+ *    Content-based weights (spim/process/fusion/weights/ContentBased.java:60-98):
+ *    per view, in its own voxel grid, normalised G(sigma2) * (G(sigma1) * I - I)^2
+ *    over extendMirrorSingle; sampled n-linearly over extendZero at fusion time
+ *    and multiplied into the blending weight (ProcessParalellPortionWeights.java).
  * ====================================================================== */
 typedef struct spim_fusion_params {
     int64_t bb_min[3];      /* bounding box (world voxels)                               */
     int64_t bb_dims[3];     /* fused image dims (after downsampling)                    */
     float   downsampling;   /* 1 = none; s = position * downsampling + bb_min            */
     int     interpolation;  /* 0 nearest neighbour, 1 n-linear (Fusion.defaultInterpolation) */
-    int     use_blending;   /* Fusion.defaultUseBlending (content-based not supported)  */
+    int     use_blending;   /* Fusion.defaultUseBlending (content-based: the _content call) */
     int     device;
     int     src_on_device;
     int     out_on_device;
@@ -435,6 +439,18 @@ void spim_fusion_params_default(spim_fusion_params* p);
  * blending); out: bb_dims voxels, x-fastest float32. */
 int spim_fuse_weighted_average(int nviews, const spim_view_source* views, const spim_fusion_params* p,
                                const float* blending_borders, const float* blending_ranges, float* out);
+
+/* ContentBased.approximateEntropy: out has dims voxels; img / out host or device pointers.
+ * sigma: (x, y, z), finite and > 0, at most 463 taps (2 * (int)(3 sigma + 0.5) + 1) per axis. */
+int spim_content_based_weights(const float* img, const int64_t dims[3], const double sigma1[3],
+                               const double sigma2[3], float* out, int device);
+
+/* spim_fuse_weighted_average with the content weight of every view (sigma1 / sigma2: nviews x 3)
+ * multiplied into its blending weight (p->use_blending 1) or used alone (0) */
+int spim_fuse_weighted_average_content(int nviews, const spim_view_source* views,
+                                       const spim_fusion_params* p, const float* blending_borders,
+                                       const float* blending_ranges, const double* sigma1,
+                                       const double* sigma2, float* out);
 
 /* ======================================================================
  * 9. PSF extraction / transformation --

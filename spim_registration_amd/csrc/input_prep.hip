@@ -24,6 +24,10 @@
 
 namespace spimdecon {
 void check_device(int dev);
+// content_weights.hip
+void check_content_sigmas(const double* sigma1, const double* sigma2);
+void content_weights_device(const float* img, const int64_t dims[3], const double* sigma1, const double* sigma2,
+                            float* out, float* tmp, hipStream_t s);
 
 namespace {
 
@@ -163,9 +167,13 @@ __global__ __launch_bounds__(kIpBlock) void k_final_weight(float* __restrict__ w
 
 // ---------------------------------------------------------------- weighted-average fusion
 // spim/process/fusion/weightedavg/ProcessParalellPortionWeight.java:86-127 (blending)
-// and ProcessParalellPortion.java:86-120 (plain mean); SURVEY 8f #3.
+// and ProcessParalellPortion.java:86-120 (plain mean); SURVEY 8f #3.  With content-based
+// weights (ProcessParalellPortionWeights.java:93-119) a view's w is the product of its
+// enabled weights, the content weight sampled n-linearly over extendZero at the same t
+// (ContentBased.java:104-110).
 struct FuseView {
     const float* src;
+    const float* cw;   // content-based weight image of the view (source grid), or null
     int sx, sy, sz;
     double inv[9], tr[3];
     float border[3], range[3];
@@ -180,8 +188,8 @@ __device__ float nearest1(const float* src, int sx, int sy, int sz, const float 
 
 __global__ __launch_bounds__(kIpBlock) void k_fuse(const FuseView* __restrict__ views, int nviews, int64_t bx,
                                                    int64_t by, int64_t bz, int64_t nx, int64_t ny, int64_t n,
-                                                   float ds, int interp, int blend, const double* __restrict__ lut,
-                                                   float* __restrict__ out) {
+                                                   float ds, int interp, int blend, int content,
+                                                   const double* __restrict__ lut, float* __restrict__ out) {
     int64_t x, y, z;
     if (!tiled_xyz(nx, ny, n / (nx * ny), x, y, z)) return;
     const int64_t i = (z * ny + y) * nx + x;
@@ -205,9 +213,13 @@ __global__ __launch_bounds__(kIpBlock) void k_fuse(const FuseView* __restrict__ 
             continue;
         const double val = interp ? double(nlinear(fv.src, fv.sx, fv.sy, fv.sz, t))
                                   : double(nearest1(fv.src, fv.sx, fv.sy, fv.sz, t));
-        if (blend) {
-            const int dims[3] = {fv.sx, fv.sy, fv.sz};
-            const double w = blend_weight(t, dims, fv.border, fv.range, lut);
+        if (blend || content) {
+            double w = 1.0;
+            if (blend) {
+                const int dims[3] = {fv.sx, fv.sy, fv.sz};
+                w = blend_weight(t, dims, fv.border, fv.range, lut);
+            }
+            if (content) w *= double(nlinear_at<kExtZero>(fv.cw, fv.sx, fv.sy, fv.sz, t[0], t[1], t[2]));
             sum += val * w;
             sumw += w;
         } else {
@@ -215,7 +227,7 @@ __global__ __launch_bounds__(kIpBlock) void k_fuse(const FuseView* __restrict__ 
             ++cnt;
         }
     }
-    out[i] = blend ? (sumw > 0.0 ? float(sum / sumw) : 0.0f) : (cnt > 0 ? float(sum / cnt) : 0.0f);
+    out[i] = (blend || content) ? (sumw > 0.0 ? float(sum / sumw) : 0.0f) : (cnt > 0 ? float(sum / cnt) : 0.0f);
 }
 
 std::vector<double> blending_lut() {
@@ -347,9 +359,14 @@ void prepare_inputs(int nviews, const spim_view_source* views, const spim_input_
     if (avg_overlap) *avg_overlap = av;
 }
 
+// sigma1 / sigma2 (nviews x 3, both or neither): content-based weights per view
 void fuse_weighted_average(int nviews, const spim_view_source* views, const spim_fusion_params* p,
-                           const float* borders, const float* ranges, float* out) {
+                           const float* borders, const float* ranges, const double* sigma1, const double* sigma2,
+                           float* out) {
     SD_CHECK(nviews >= 1 && views && p && out, SPIMDECON_ERR_ARG, "null argument");
+    const bool content = sigma1 != nullptr;
+    if (content)
+        for (int v = 0; v < nviews; ++v) check_content_sigmas(sigma1 + 3 * v, sigma2 + 3 * v);
     SD_CHECK(!p->use_blending || (borders && ranges), SPIMDECON_ERR_ARG, "blending needs borders and ranges");
     SD_CHECK(p->bb_dims[0] >= 1 && p->bb_dims[1] >= 1 && p->bb_dims[2] >= 1, SPIMDECON_ERR_ARG, "bad bounding box");
     SD_CHECK(p->interpolation == 0 || p->interpolation == 1, SPIMDECON_ERR_ARG, "interpolation must be 0 or 1");
@@ -366,7 +383,7 @@ void fuse_weighted_average(int nviews, const spim_view_source* views, const spim
     const std::vector<double> lut = blending_lut();
     DBuf<double> dlut(lut.size());
     SD_HIP(hipMemcpyAsync(dlut.p, lut.data(), lut.size() * 8, hipMemcpyHostToDevice, s));
-    std::vector<DBuf<float>> srcs(nviews);
+    std::vector<DBuf<float>> srcs(nviews), cws(content ? nviews : 0);
     std::vector<FuseView> fv(nviews);
     for (int v = 0; v < nviews; ++v) {
         const spim_view_source& vs = views[v];
@@ -384,6 +401,14 @@ void fuse_weighted_average(int nviews, const spim_view_source* views, const spim
         fv[v].sx = int(vs.dims[0]);
         fv[v].sy = int(vs.dims[1]);
         fv[v].sz = int(vs.dims[2]);
+        fv[v].cw = nullptr;
+        if (content) {
+            // every view's weight image stays resident for k_fuse; released on return
+            cws[v].alloc(sn);
+            DBuf<float> tmp(sn);
+            content_weights_device(fv[v].src, vs.dims, sigma1 + 3 * v, sigma2 + 3 * v, cws[v].p, tmp.p, s);
+            fv[v].cw = cws[v].p;
+        }
         const AffineInv a = invert_model(vs.model);
         std::memcpy(fv[v].inv, a.inv, sizeof(a.inv));
         std::memcpy(fv[v].tr, a.tr, sizeof(a.tr));
@@ -404,7 +429,7 @@ void fuse_weighted_average(int nviews, const spim_view_source* views, const spim
     SD_CHECK(tiled_blocks(nx, ny, nz) < (int64_t(1) << 31), SPIMDECON_ERR_ARG, "bounding box too large");
     hipLaunchKernelGGL(k_fuse, dim3(unsigned(tiled_blocks(nx, ny, n / (nx * ny)))), dim3(kIpBlock), 0, s, dfv.p,
                        nviews, p->bb_min[0], p->bb_min[1], p->bb_min[2], nx, ny, n, p->downsampling,
-                       p->interpolation, p->use_blending ? 1 : 0, dlut.p, o);
+                       p->interpolation, p->use_blending ? 1 : 0, content ? 1 : 0, dlut.p, o);
     SD_HIP(hipGetLastError());
     if (!p->out_on_device) SD_HIP(hipMemcpyAsync(out, o, n * 4, hipMemcpyDeviceToHost, s));
     SD_HIP(hipStreamSynchronize(s));
@@ -426,7 +451,19 @@ extern "C" void spim_fusion_params_default(spim_fusion_params* p) {
 extern "C" int spim_fuse_weighted_average(int nviews, const spim_view_source* views, const spim_fusion_params* p,
                                           const float* blending_borders, const float* blending_ranges,
                                           float* out) {
-    return guarded([&] { fuse_weighted_average(nviews, views, p, blending_borders, blending_ranges, out); });
+    return guarded([&] {
+        fuse_weighted_average(nviews, views, p, blending_borders, blending_ranges, nullptr, nullptr, out);
+    });
+}
+
+extern "C" int spim_fuse_weighted_average_content(int nviews, const spim_view_source* views,
+                                                  const spim_fusion_params* p, const float* blending_borders,
+                                                  const float* blending_ranges, const double* sigma1,
+                                                  const double* sigma2, float* out) {
+    return guarded([&] {
+        SD_CHECK(sigma1 && sigma2, SPIMDECON_ERR_ARG, "content-based fusion needs sigma1 and sigma2");
+        fuse_weighted_average(nviews, views, p, blending_borders, blending_ranges, sigma1, sigma2, out);
+    });
 }
 
 extern "C" void spim_input_params_default(spim_input_params* p) {

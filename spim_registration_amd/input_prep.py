@@ -106,11 +106,70 @@ def _prepare_inputs_device(lib, srcs, models, bb_min, bb_dims, blending_border, 
     return imgs, ws, {"osem": osem.value, "min_overlap": mn.value, "avg_overlap": av.value}
 
 
+def content_based_sigmas(voxel_size, sigma1=(20, 20, 20), sigma2=(40, 40, 40), adjust: bool = True):
+    """ProcessFusion.getContentBased (spim/process/fusion/weightedavg/ProcessFusion.java:89-107):
+    with ``adjust`` (defaultAdjustContentBasedSigmaForAnisotropy) the sigmas of axes 0 and 1
+    -- the reference's loop stops at 2 -- are divided by voxel_size[d] / min(voxel_size).
+    voxel_size, sigmas: (x, y, z).  Returns (sigma1, sigma2) as lists of floats."""
+    vs = [float(v) for v in voxel_size]
+    s1, s2 = [float(s) for s in sigma1], [float(s) for s in sigma2]
+    if len(vs) != 3 or len(s1) != 3 or len(s2) != 3:
+        raise ValueError("voxel_size, sigma1 and sigma2 take 3 values (x, y, z)")
+    min_res = min(vs)
+    if adjust:
+        for d in range(2):
+            s1[d] /= vs[d] / min_res
+            s2[d] /= vs[d] / min_res
+    return s1, s2
+
+
+def _sigma3(sigma, count=1):
+    a = np.ascontiguousarray(np.asarray(sigma, np.float64))
+    if a.size == 3 and count > 1:
+        a = np.ascontiguousarray(np.tile(a.reshape(1, 3), (count, 1)))
+    if a.size != 3 * count:
+        raise ValueError(f"sigma needs 3 values (x, y, z){' per view' if count > 1 else ''}")
+    return a
+
+
+def content_based_weights(img, sigma1=(20, 20, 20), sigma2=(40, 40, 40), device: int = 0):
+    """Content-based fusion weights of one view (ContentBased.approximateEntropy,
+    spim/process/fusion/weights/ContentBased.java:60-98): the [z, y, x] float32 image
+    normalise(G(sigma2) * (G(sigma1) * img - img)^2), Gaussians over extendMirrorSingle,
+    sigmas (x, y, z).  A torch tensor on the GPU is read in place and the weights come
+    back as a tensor on the same device; anything else goes through numpy."""
+    lib = _lib.load()
+    s1, s2 = _sigma3(sigma1), _sigma3(sigma2)
+    pd = lambda a: a.ctypes.data_as(_lib._pd)
+    if hasattr(img, "is_cuda") and img.is_cuda:
+        import torch
+        if img.dim() != 3:
+            raise ValueError("img must be 3D [z, y, x]")
+        img = img.contiguous().float()
+        torch.cuda.synchronize(img.device)   # the library runs on its own stream
+        dims = (C.c_int64 * 3)(img.shape[2], img.shape[1], img.shape[0])
+        out = torch.empty_like(img)
+        check(lib.spim_content_based_weights(img.data_ptr(), dims, pd(s1), pd(s2), out.data_ptr(),
+                                             img.device.index or 0))
+        return out
+    img = np.ascontiguousarray(img, np.float32)
+    if img.ndim != 3:
+        raise ValueError("img must be 3D [z, y, x]")
+    dims = (C.c_int64 * 3)(img.shape[2], img.shape[1], img.shape[0])
+    out = np.empty_like(img)
+    check(lib.spim_content_based_weights(img.ctypes.data, dims, pd(s1), pd(s2), out.ctypes.data, int(device)))
+    return out
+
+
 def fuse_weighted_average(srcs, models, bb_min, bb_dims, downsampling: float = 1.0, interpolation: int = 1,
                           use_blending: bool = True, blending_borders=None, blending_ranges=None,
-                          device: int = 0) -> np.ndarray:
+                          device: int = 0, use_content_based: bool = False, content_sigma1=None,
+                          content_sigma2=None) -> np.ndarray:
     """Weighted-average fusion (spim/process/fusion/weightedavg/ProcessParalell*.java):
-    [z, y, x] float32 fused volume.  blending_borders / ranges: (x, y, z) per view."""
+    [z, y, x] float32 fused volume.  blending_borders / ranges: (x, y, z) per view.
+    use_content_based: every view's content-based weight (content_based_weights with
+    content_sigma1 / content_sigma2, (x, y, z) for all views or one triple per view;
+    default 20 / 40) is multiplied into its blending weight, or used alone."""
     lib = _lib.load()
     V = len(srcs)
     srcs = [np.ascontiguousarray(s, np.float32) for s in srcs]
@@ -132,6 +191,13 @@ def fuse_weighted_average(srcs, models, bb_min, bb_dims, downsampling: float = 1
         b = np.ascontiguousarray(np.asarray(blending_borders, np.float32).reshape(V, 3))
         r = np.ascontiguousarray(np.asarray(blending_ranges, np.float32).reshape(V, 3))
     out = np.empty((int(bb_dims[2]), int(bb_dims[1]), int(bb_dims[0])), np.float32)
+    if use_content_based:
+        s1 = _sigma3((20, 20, 20) if content_sigma1 is None else content_sigma1, V)
+        s2 = _sigma3((40, 40, 40) if content_sigma2 is None else content_sigma2, V)
+        check(lib.spim_fuse_weighted_average_content(
+            V, views, C.byref(p), fptr(b) if b is not None else None, fptr(r) if r is not None else None,
+            s1.ctypes.data_as(_lib._pd), s2.ctypes.data_as(_lib._pd), fptr(out)))
+        return out
     check(lib.spim_fuse_weighted_average(V, views, C.byref(p), fptr(b) if b is not None else None,
                                          fptr(r) if r is not None else None, fptr(out)))
     return out
