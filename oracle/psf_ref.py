@@ -62,9 +62,10 @@ def extract_psf_local_batched(img: np.ndarray, locations, size, chunk: int = 512
 def normalize(psf: np.ndarray) -> np.ndarray:
     """:281-299 -- (v - min) / (max - min) in double, stored as float."""
     v = psf.astype(np.float64)
-    finite = v[~np.isnan(v)]                      # NaN never wins `v < min` / `v > max`
-    mn = finite.min() if finite.size else np.finfo(np.float64).max
-    mx = finite.max() if finite.size else -np.finfo(np.float64).max
+    big = np.finfo(np.float64).max                # the running `v < min` / `v > max` from
+    finite = v[~np.isnan(v)]                      # +-Double.MAX_VALUE: NaN never wins, nor
+    mn = min(finite.min(), big) if finite.size else big      # does +inf as a minimum or
+    mx = max(finite.max(), -big) if finite.size else -big    # -inf as a maximum
     with np.errstate(invalid="ignore", divide="ignore"):
         return ((v - mn) / (mx - mn)).astype(np.float32)
 
@@ -129,7 +130,9 @@ def average_transformed_psf(psfs):
 
 def max_projection(img: np.ndarray, min_dim: int = -1):
     """:110-162 -- max along min_dim (x=0, y=1, z=2; < 0: the first smallest
-    dimension); the remaining dims keep their order."""
+    dimension); the remaining dims keep their order.  The maximum is a running
+    `value > maxValue` from -Double.MAX_VALUE in double (:152-161), stored through
+    setReal into a float: a NaN is skipped, a line of NaN only gives -inf."""
     dims = [img.shape[2], img.shape[1], img.shape[0]]
     if min_dim < 0:
         min_dim = 0
@@ -137,4 +140,7 @@ def max_projection(img: np.ndarray, min_dim: int = -1):
             if dims[d] < dims[min_dim]:
                 min_dim = d
     axis = 2 - min_dim
-    return img.max(axis=axis).astype(np.float32), min_dim
+    v = np.asarray(img, np.float32).astype(np.float64)
+    mx = np.where(np.isnan(v), -np.inf, v).max(axis=axis)
+    with np.errstate(over="ignore"):
+        return np.maximum(mx, -np.finfo(np.float64).max).astype(np.float32), min_dim

@@ -30,17 +30,16 @@ def test_extract_psf_matches_oracle(gpu, size):
     orig, trans = psf.extract_psf(img, locs, size, ROT)
     eo, et = pr.extract_next_img(img, ROT, locs, size)
     assert orig.shape == eo.shape and trans.shape == et.shape
-    np.testing.assert_allclose(orig, eo, rtol=1e-6, atol=1e-7)
-    np.testing.assert_allclose(trans, et, rtol=1e-5, atol=1e-6)
-    assert np.mean(orig == eo) > 0.99 and orig.max() == 1.0 and orig.min() == 0.0
+    np.testing.assert_array_equal(orig, eo)                       # bit for bit: DESIGN.md section 2
+    np.testing.assert_array_equal(trans, et)
+    assert orig.max() == 1.0 and orig.min() == 0.0
 
 
 def test_extract_psf_identity_model_and_device_input(gpu):
     img, locs = bead_view(cid=22)
     orig, trans = psf.extract_psf(torch.from_numpy(img).cuda(), locs, (11, 11, 15), np.eye(3, 4))
     np.testing.assert_array_equal(orig, trans)                    # identity keeps the centre voxel
-    np.testing.assert_allclose(orig, pr.extract_next_img(img, np.eye(3, 4), locs, (11, 11, 15))[0],
-                               rtol=1e-6, atol=1e-7)
+    np.testing.assert_array_equal(orig, pr.extract_next_img(img, np.eye(3, 4), locs, (11, 11, 15))[0])
 
 
 def test_extract_psf_no_beads_is_nan(gpu):
@@ -58,7 +57,7 @@ def test_transform_psf_matches_oracle(gpu, model):
     got = psf.transform_psf(p, model)
     want = pr.transform_psf(p, model)
     assert got.shape == want.shape and all(n % 2 == 1 for n in got.shape)
-    np.testing.assert_allclose(got, want, rtol=1e-5, atol=1e-6)
+    np.testing.assert_array_equal(got, want)
 
 
 def test_average_transformed_psf_and_max_projection(gpu):
@@ -83,9 +82,9 @@ def test_extract_psf_many_beads_two_phase(gpu, nbeads):
     few = psf.extract_psf(img, locs[:64], (9, 9, 11), ROT)[0]          # per-voxel loop path
     orig, trans = psf.extract_psf(img, locs, (9, 9, 11), ROT)
     eo, et = pr.extract_next_img(img, ROT, locs, (9, 9, 11))
-    np.testing.assert_allclose(orig, eo, rtol=1e-6, atol=1e-7)
-    np.testing.assert_allclose(trans, et, rtol=1e-5, atol=1e-6)
-    np.testing.assert_allclose(few, pr.extract_next_img(img, ROT, locs[:64], (9, 9, 11))[0], rtol=1e-6, atol=1e-7)
+    np.testing.assert_array_equal(orig, eo)
+    np.testing.assert_array_equal(trans, et)
+    np.testing.assert_array_equal(few, pr.extract_next_img(img, ROT, locs[:64], (9, 9, 11))[0])
 
 
 def test_extract_psfs_batch_equals_per_view(gpu):

@@ -241,9 +241,9 @@ def test_c4_timepoint_8view_768(gpu):
     for (orig_g, tr_g), v, lc in zip(got, sel, locs):
         orig = psf_ref.normalize(psf_ref.extract_psf_local_batched(hv[v], lc, (19, 19, 25)))
         want = psf_ref.transform_psf(orig, models[v])
-        np.testing.assert_allclose(orig_g, orig, rtol=1e-5, atol=1e-6)
+        np.testing.assert_array_equal(orig_g, orig)               # bit for bit: DESIGN.md section 2
         assert tr_g.shape == want.shape == res.psfs[v].shape
-        np.testing.assert_allclose(tr_g, want, rtol=1e-5, atol=1e-6)
+        np.testing.assert_array_equal(tr_g, want)
     log("PSF extraction matches the oracle")
     del hv, views
     release()
