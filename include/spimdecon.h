@@ -372,6 +372,46 @@ int spim_set_java_version(int jdk);
 int spim_java_double_to_string(double d, char* out, int cap);
 
 /* ======================================================================
+ * 6b. Difference-of-Mean bead detection ("Difference-of-Mean (Integral image based)") --
+ *     spim/process/interestpointdetection/ProcessDOM.java:36-117,
+ *     mpicbg/spim/segmentation/DOM.java:29-171, IntegralImage3d.java:60-210:
+ *     dom = (float) s2 / d2 - (float) s1 / d1, s_b the sum of (int) voxel over box b
+ *     (as long), d_b = (float)(box voxels) * (max - min); zero where the boxes do not
+ *     fit.  The image is not normalised.  Bit-exact against the reference's arithmetic.
+ * ====================================================================== */
+typedef struct spim_dom_params {
+    int     radius1;         /* default 2 (DifferenceOfMean.java:29)                 */
+    int     radius2;         /* default 3 (:30); radius1 > radius2 is legal          */
+    float   threshold;       /* default 0.02 (:31); used as given with either localization */
+    int     localization;    /* 0 = none, 1 = quadratic (kept when |fit| > threshold) */
+    double  image_sigma[3];  /* default 0.5 each: diameter = max(3 | 5, round(radius * 0.5 / sigma) * 2 + 1) */
+    int32_t find_min;
+    int32_t find_max;
+    double  min_intensity;   /* NaN -> image min/max                                */
+    double  max_intensity;
+    int     ij_threads;      /* peak ordering, as spim_dog_params                   */
+    int     device;
+} spim_dom_params;
+
+void spim_dom_params_default(spim_dom_params* p);
+
+/* The box diameters per axis (ProcessDOM.java:71-78): s1 from radius1 (at least 3), s2
+ * from radius2 (at least 5).  Host only: needs no GPU. */
+int spim_dom_diameters(const spim_dom_params* p, int32_t s1[3], int32_t s2[3]);
+
+/* As spim_dog_compute / spim_dog_interest_points (host or device pointers, optional
+ * image out, the capacity rule, the workspace of spim_dog_release_workspace) with the
+ * DOM image in place of the DoG image.  Diameters up to 33 voxels per axis; beyond, and
+ * for any bad argument (null, dims < 1, radius < 1, image_sigma <= 0 or not finite,
+ * ij_threads < 1, localization other than 0 / 1), SPIMDECON_ERR_ARG before any GPU work.
+ * A volume the boxes do not fit into gives an all-zero image and no peaks (status OK). */
+int spim_dom_compute(const float* img, const int64_t* dims, const spim_dom_params* p,
+                     float* dom_out, spim_peak* peaks, int64_t max_peaks, int64_t* npeaks);
+int spim_dom_interest_points(const float* img, const int64_t* dims, const spim_dom_params* p,
+                             float* dom_out, spim_interest_point* out, int64_t max_out,
+                             int64_t* nout);
+
+/* ======================================================================
  * 7. Deconvolution input preparation --
  *    spim/process/fusion/deconvolution/ProcessForDeconvolution.java:159-384:
  *    each view resampled into the fused bounding box through the inverse of

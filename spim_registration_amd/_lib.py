@@ -59,6 +59,22 @@ class DogParams(C.Structure):
     ]
 
 
+class DomParams(C.Structure):
+    _fields_ = [
+        ("radius1", C.c_int),
+        ("radius2", C.c_int),
+        ("threshold", C.c_float),
+        ("localization", C.c_int),
+        ("image_sigma", C.c_double * 3),
+        ("find_min", C.c_int32),
+        ("find_max", C.c_int32),
+        ("min_intensity", C.c_double),
+        ("max_intensity", C.c_double),
+        ("ij_threads", C.c_int),
+        ("device", C.c_int),
+    ]
+
+
 class Peak(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32),
                 ("intensity", C.c_float), ("is_min", C.c_int32), ("is_max", C.c_int32)]
@@ -143,6 +159,11 @@ SIGNATURES = {
     "spim_dog_interest_points_ext": (C.c_int, [_pf, _pi64, C.POINTER(DogParams), _i32, _pf,
                                                C.POINTER(InterestPointC), _i64, _pi64]),
     "spim_dog_release_workspace": (C.c_int, [C.c_int]),
+    "spim_dom_params_default": (None, [C.POINTER(DomParams)]),
+    "spim_dom_diameters": (C.c_int, [C.POINTER(DomParams), C.POINTER(_i32), C.POINTER(_i32)]),
+    "spim_dom_compute": (C.c_int, [_pf, _pi64, C.POINTER(DomParams), _pf, C.POINTER(Peak), _i64, _pi64]),
+    "spim_dom_interest_points": (C.c_int, [_pf, _pi64, C.POINTER(DomParams), _pf,
+                                           C.POINTER(InterestPointC), _i64, _pi64]),
     "spim_psf_release_workspace": (C.c_int, [C.c_int]),
     "spim_save_interest_points": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(InterestPointC),
                                             C.POINTER(C.c_int32), C.c_int64]),

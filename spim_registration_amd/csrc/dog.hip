@@ -30,6 +30,7 @@
 #include <vector>
 
 #include "common.hpp"
+#include "dog_detect.hpp"
 
 namespace spimdecon {
 
@@ -45,10 +46,6 @@ namespace {
 
 constexpr int kBlock = 256;
 enum Oob { OOB_ZERO = 0, OOB_VALUE = 1, OOB_BORDER = 2, OOB_MIRROR = 3 };
-
-struct Dims3 {
-    int64_t nx, ny, nz;
-};
 
 __device__ __forceinline__ int64_t ext_index(int64_t i, int64_t n, int mode, bool& outside) {
     outside = false;
@@ -704,23 +701,7 @@ __global__ __launch_bounds__(256, 4) void k_dog_xy(Dims3 d, const float* __restr
     }
 }
 
-struct PeakOut {   // (k_dog_z's cand_flush writes it as three int pairs)
-    int32_t x, y, z;
-    float intensity;
-    int32_t is_min, is_max;
-};
-
-// candidate sink: unordered append of (key, record); count may exceed cap (the host reruns)
-struct PeakSink {
-    float minv;
-    int want_min, want_max, T;
-    uint64_t* keys;
-    uint32_t* vals;
-    PeakOut* recs;
-    unsigned* count;
-    unsigned cap;
-};
-
+// (PeakOut and the candidate sink PeakSink: dog_detect.hpp)
 // one wave-wide append; every lane of the wave must call it
 __device__ __forceinline__ void sink_append(const PeakSink& pk, bool flag, int x, int y, int z, uint64_t flat,
                                             float c, int sp) {
@@ -1564,12 +1545,7 @@ void separable_convolve(float* image, const float* kx, const float* ky, const fl
 // IPD/Localization.java:47-88 (imglib1 SubpixelLocalization, maxNumMoves 10,
 // allowMaximaTolerance); finite differences and 3x3 inverse as in the reference's
 // own fit, mpicbg/spim/registration/bead/laplace/LaPlaceFunctions.java:30-170,243-466.
-// One thread per peak; all fit arithmetic in double, -ffp-contract=off.
-struct LocOut {
-    float pos[3];
-    float value;
-};
-
+// One thread per peak; all fit arithmetic in double, -ffp-contract=off.  (LocOut: dog_detect.hpp)
 constexpr int kLocMaxMoves = 10;
 constexpr double kLocTolerance = 0.01;
 
@@ -1659,45 +1635,7 @@ bool is_device_ptr(const void* p, int dev) {
     return at.type == hipMemoryTypeDevice && at.device == dev;
 }
 
-// Per-device DoG workspace, grown on demand and kept between calls (a 768^3 view needs
-// ~3.6 GB of G12 plus the candidate lists; hipMalloc / hipFree of that per call cost
-// more than the DoG itself).  One call at a time per device holds its mutex;
-// spim_dog_release_workspace frees it.
-struct DogWork {
-    std::mutex mu;
-    DBuf<float> in, dog, taps, mm, tmp_a, tmp_b, tmp_c, tmp_d;
-    DBuf<float2> g12;
-    DBuf<uint64_t> keys, keys_sorted;
-    DBuf<uint32_t> vals, vals_sorted;
-    DBuf<PeakOut> recs, peaks;
-    DBuf<unsigned> count;
-    DBuf<unsigned char> sort_tmp;
-    DBuf<LocOut> loc;                      // localisation results
-    DBuf<spim_interest_point> ips, ips_sel;  // interest points before / after the threshold
-    DBuf<unsigned char> flags, sel_tmp;
-    DBuf<int> nsel;
-    DBuf<PeakSink> sink;                   // k_dog_z's sink, read at its flushes
-    // the calls' stream, created once (a stream per call cost ~1 ms of host time per
-    // 768^3 call: r3l trace, 1.17 ms before the first copy)
-    hipStream_t stream = nullptr;
-    hipStream_t get_stream() {
-        if (!stream) SD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        return stream;
-    }
-    void release() {
-        if (stream) {
-            (void)hipStreamDestroy(stream);
-            stream = nullptr;
-        }
-        for (DBuf<float>* b : {&in, &dog, &taps, &mm, &tmp_a, &tmp_b, &tmp_c, &tmp_d}) b->release();
-        g12.release();
-        keys.release(); keys_sorted.release(); vals.release(); vals_sorted.release();
-        recs.release(); peaks.release(); count.release(); sort_tmp.release();
-        loc.release(); ips.release(); ips_sel.release(); flags.release(); sel_tmp.release(); nsel.release();
-        sink.release();
-    }
-};
-
+// (the per-device workspace DogWork: dog_detect.hpp)
 std::mutex g_dogwork_mu;
 // never destroyed (as legacy.cpp's g_ctx): no hipFree / hipStreamDestroy from a static
 // destructor racing the HIP runtime's own teardown at process exit
@@ -1710,23 +1648,87 @@ DogWork& dog_work(int dev) {
     return *w;
 }
 
-template <typename T>
-void grow(DBuf<T>& b, size_t n) {
-    if (b.n < n) b.alloc(n);
-}
-
-// the DoG image (on the device) and the reference-ordered candidate list (on the device)
-struct DogRun {
-    Dims3 d{};
-    const float* dog = nullptr;   // nullptr when neither localisation nor the image was asked for
-    int64_t np = 0;
-    const PeakOut* dpeaks = nullptr;
-};
-
 int bits_for(uint64_t v) {
     int b = 0;
     while (b < 64 && (v >> b) != 0) ++b;
     return b;
+}
+
+// ---------------------------------------------------------------- the shared detection stage
+// The candidate pass of a detector: `launch(pk, attempt)` enqueues the kernel(s) that append
+// to the sink pk; a count beyond the capacity reruns it once with room for every candidate.
+template <typename Launch>
+unsigned collect_candidates(DogWork& w, int64_t n, float min_peak, int wmin, int wmax, int T, hipStream_t s,
+                            Launch&& launch) {
+    grow(w.count, 1);
+    unsigned cap = unsigned(std::min<int64_t>(std::max<int64_t>(int64_t(1) << 16, n / 256), int64_t(1) << 30));
+    cap = std::max<unsigned>(cap, unsigned(std::min<size_t>(w.recs.n, size_t(1) << 30)));
+    unsigned total = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        grow(w.keys, cap);
+        grow(w.vals, cap);
+        grow(w.recs, cap);
+        SD_HIP(hipMemsetAsync(w.count.p, 0, sizeof(unsigned), s));
+        const PeakSink pk{min_peak, wmin, wmax, T, w.keys.p, w.vals.p, w.recs.p, w.count.p, cap};
+        launch(pk, attempt);
+        SD_HIP(hipGetLastError());
+        SD_HIP(hipMemcpyAsync(&total, w.count.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        SD_HIP(hipStreamSynchronize(s));
+        if (total <= cap) break;
+        cap = total;          // rerun with room for every candidate (the image is already stored)
+    }
+    return total;
+}
+
+// k_dog_peaks addresses the image through one buffer resource with 32-bit plane offsets: below 4 GiB
+bool peaks_kernel_ok(const Dims3& d) { return uint64_t(d.nx * d.ny * d.nz) * 4u < 0xffffffffull; }
+
+// candidates of a stored image: k_dog_peaks, or k_peaks_append where its limits are not met
+void stored_candidates(DogWork& w, const Dims3& d, const float* dogp, bool peaks_kernel, const PeakSink& pk,
+                       hipStream_t s) {
+    if (peaks_kernel) {
+        grow(w.sink, 1);
+        SD_HIP(hipMemcpyAsync(w.sink.p, &pk, sizeof(pk), hipMemcpyHostToDevice, s));   // (synchronised by the caller)
+        const int want = pk.want_min | (pk.want_max << 1);
+        // (the ring test of k_dog_z over the stored image measured 1.19 vs 0.42 ms)
+        if (d.nx >= 3 && d.ny >= 3 && d.nz >= 3) {   // (else no voxel has 26 neighbours)
+            constexpr int zcp = 64;
+            const int64_t nwave = ceil_div(d.nx - 2, int64_t(62)) * ceil_div(d.ny - 2, int64_t(kDpkY)) *
+                                  ceil_div(d.nz - 2, int64_t(zcp));
+            const dim3 gp(unsigned(ceil_div(nwave, int64_t(4))));
+            hipLaunchKernelGGL((k_dog_peaks<kDpkY, kDpkPD>), gp, dim3(256), 0, s, d, dogp, zcp, pk.minv, want, w.sink.p, 1);
+        }
+    } else {
+        hipLaunchKernelGGL(k_peaks_append, dim3(grid_of(d.nx * d.ny * d.nz)), dim3(kBlock), 0, s, dogp, d, pk);
+    }
+}
+
+// reference order: ascending (x % T) << 40 | flat
+void sort_candidates(DogWork& w, unsigned total, int T, hipStream_t s, DogRun& r) {
+    r.np = total;
+    if (total > 0) {
+        grow(w.keys_sorted, total);
+        grow(w.vals_sorted, total);
+        grow(w.peaks, total);
+        const int end_bit = 40 + bits_for(uint64_t(T - 1));
+        const size_t tb = peak_sort_temp_bytes(total, end_bit);
+        grow(w.sort_tmp, std::max<size_t>(tb, 1));
+        peak_sort(w.sort_tmp.p, tb, w.keys.p, w.keys_sorted.p, w.vals.p, w.vals_sorted.p, total, end_bit, s);
+        hipLaunchKernelGGL(k_gather_peaks, dim3(unsigned(ceil_div(total, 256))), dim3(256), 0, s, w.recs.p,
+                           w.vals_sorted.p, int64_t(total), w.peaks.p);
+        SD_HIP(hipGetLastError());
+        r.dpeaks = w.peaks.p;
+    }
+}
+
+void detect_stored(DogWork& w, const Dims3& d, const float* img, float min_peak, int want_min, int want_max, int T,
+                   hipStream_t s, DogRun& r) {
+    const bool pkk = peaks_kernel_ok(d);
+    const unsigned total = collect_candidates(w, d.nx * d.ny * d.nz, min_peak, want_min, want_max, T, s,
+                                              [&](const PeakSink& pk, int) { stored_candidates(w, d, img, pkk, pk, s); });
+    r.d = d;
+    r.dog = img;
+    sort_candidates(w, total, T, s, r);
 }
 
 // oob: OOB_MIRROR (the reference's accurate mode) or OOB_BORDER (its approximate mode)
@@ -1826,9 +1828,6 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, in
             dogp = w.dog.p;
         }
     }
-    grow(w.count, 1);
-    unsigned cap = unsigned(std::min<int64_t>(std::max<int64_t>(int64_t(1) << 16, n / 256), int64_t(1) << 30));
-    cap = std::max<unsigned>(cap, unsigned(std::min<size_t>(w.recs.n, size_t(1) << 30)));
     const int T = p->ij_threads;
     const int wmin = p->find_min ? 1 : 0, wmax = p->find_max ? 1 : 0;
     const bool fused = (K == 7 || K == 15 || K == 31) && n < (int64_t(1) << 32) && d.ny <= 65535 * 32 &&
@@ -1848,7 +1847,6 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, in
     const bool zsl = d.nz > K / 2 && d.nx * d.ny * 8 < (int64_t(1) << 31);
     const dim3 gz(unsigned(std::max<int64_t>(1, ceil_div(d.nx - 2, bx - 2))),
                   unsigned(std::max<int64_t>(1, ceil_div(d.ny - 2, bz_y - 2))), unsigned(ceil_div(d.nz, zc)));
-    bool store_dog = need_dog;
     // the split z stage (default): k_dog_zconv stores the DoG of every voxel, then k_dog_z
     // tests over the stored image (SPIMDECON_DOG_SPLIT=0: the fused k_dog_z); a candidate
     // overflow reruns the test pass only
@@ -1906,27 +1904,12 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, in
         sep_pass(d, 2, w.tmp_c.p, w.tmp_d.p, kp(2, 0), kp(2, 1), K, oob, 0.f, dogp, nullptr, true, kinv,
                  nullptr, s);
     }
-    unsigned total = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        grow(w.keys, cap);
-        grow(w.vals, cap);
-        grow(w.recs, cap);
-        SD_HIP(hipMemsetAsync(w.count.p, 0, sizeof(unsigned), s));
-        const PeakSink pk{min_peak, wmin, wmax, T, w.keys.p, w.vals.p, w.recs.p, w.count.p, cap};
+    // a candidate overflow reruns the pass with the DoG already stored
+    const unsigned total = collect_candidates(w, n, min_peak, wmin, wmax, T, s, [&](const PeakSink& pk, int attempt) {
         if (split) {
-            grow(w.sink, 1);
-            SD_HIP(hipMemcpyAsync(w.sink.p, &pk, sizeof(pk), hipMemcpyHostToDevice, s));   // (synchronised below)
-            const int want = wmin | (wmax << 1);
-            // (the ring test of k_dog_z over the stored image measured 1.19 vs 0.42 ms)
-            if (d.nx >= 3 && d.ny >= 3 && d.nz >= 3) {   // (else no voxel has 26 neighbours)
-                constexpr int zcp = 64;
-                const int64_t nwave = ceil_div(d.nx - 2, int64_t(62)) * ceil_div(d.ny - 2, int64_t(kDpkY)) *
-                                      ceil_div(d.nz - 2, int64_t(zcp));
-                const dim3 gp(unsigned(ceil_div(nwave, int64_t(4))));
-                hipLaunchKernelGGL((k_dog_peaks<kDpkY, kDpkPD>), gp, dim3(256), 0, s, d, dogp, zcp, min_peak, want, w.sink.p, 1);
-            }
+            stored_candidates(w, d, dogp, true, pk, s);
         } else if (fused) {
-            float* dst = store_dog ? dogp : nullptr;
+            float* dst = need_dog && attempt == 0 ? dogp : nullptr;
             grow(w.sink, 1);
             SD_HIP(hipMemcpyAsync(w.sink.p, &pk, sizeof(pk), hipMemcpyHostToDevice, s));   // (synchronised below)
             const bool one = uint64_t(n) * 4u < 0x80000000ull;
@@ -1941,38 +1924,29 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, in
 #undef SD_DOGZ3
 #undef SD_DOGZ4
         } else {
-            hipLaunchKernelGGL(k_peaks_append, dim3(grid_of(n)), dim3(kBlock), 0, s, dogp, d, pk);
+            stored_candidates(w, d, dogp, false, pk, s);
         }
-        SD_HIP(hipGetLastError());
-        SD_HIP(hipMemcpyAsync(&total, w.count.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        SD_HIP(hipStreamSynchronize(s));
-        if (total <= cap) break;
-        cap = total;          // rerun with room for every candidate (the DoG is already stored)
-        store_dog = false;
-    }
-    // reference order: ascending (x % T) << 40 | flat
-    r.np = total;
+    });
     r.dog = dogp;
-    if (total > 0) {
-        grow(w.keys_sorted, total);
-        grow(w.vals_sorted, total);
-        grow(w.peaks, total);
-        const int end_bit = 40 + bits_for(uint64_t(T - 1));
-        const size_t tb = peak_sort_temp_bytes(total, end_bit);
-        grow(w.sort_tmp, std::max<size_t>(tb, 1));
-        peak_sort(w.sort_tmp.p, tb, w.keys.p, w.keys_sorted.p, w.vals.p, w.vals_sorted.p, total, end_bit, s);
-        hipLaunchKernelGGL(k_gather_peaks, dim3(unsigned(ceil_div(total, 256))), dim3(256), 0, s, w.recs.p,
-                           w.vals_sorted.p, int64_t(total), w.peaks.p);
-        SD_HIP(hipGetLastError());
-        r.dpeaks = w.peaks.p;
-    }
+    sort_candidates(w, total, T, s, r);
     if (dog_out && !dog_dev) SD_HIP(hipMemcpyAsync(dog_out, dogp, n * 4, hipMemcpyDefault, s));
 }
 
-struct StreamHolder {   // the workspace's stream (held under its mutex)
-    hipStream_t s = nullptr;
-    explicit StreamHolder(DogWork& w) : s(w.get_stream()) {}
-};
+void peaks_to_host(const DogRun& r, spim_peak* peaks, int64_t max_peaks, int64_t* npeaks, hipStream_t s) {
+    *npeaks = r.np;
+    const int64_t m = peaks ? std::min(r.np, max_peaks) : 0;
+    std::vector<PeakOut> hp(std::max<int64_t>(m, 0));
+    if (m > 0) SD_HIP(hipMemcpyAsync(hp.data(), r.dpeaks, m * sizeof(PeakOut), hipMemcpyDeviceToHost, s));
+    SD_HIP(hipStreamSynchronize(s));
+    for (int64_t i = 0; i < m; ++i) {
+        peaks[i].x = hp[i].x;
+        peaks[i].y = hp[i].y;
+        peaks[i].z = hp[i].z;
+        peaks[i].intensity = hp[i].intensity;
+        peaks[i].is_min = hp[i].is_min;
+        peaks[i].is_max = hp[i].is_max;
+    }
+}
 
 // DifferenceOfGaussianNewPeakFinder.getSimplePeaks level: candidates with
 // |v| >= threshold (localization 0) or threshold / 10 (localization 1)
@@ -1994,19 +1968,7 @@ void dog_compute(const float* img, const int64_t* dims, const spim_dog_params* p
     StreamHolder sh(w);
     DogRun r;
     dog_run(img, dims, p, oob, dog_out, dog_out != nullptr, sh.s, w, r);
-    *npeaks = r.np;
-    const int64_t m = peaks ? std::min(r.np, max_peaks) : 0;
-    std::vector<PeakOut> hp(std::max<int64_t>(m, 0));
-    if (m > 0) SD_HIP(hipMemcpyAsync(hp.data(), r.dpeaks, m * sizeof(PeakOut), hipMemcpyDeviceToHost, sh.s));
-    SD_HIP(hipStreamSynchronize(sh.s));
-    for (int64_t i = 0; i < m; ++i) {
-        peaks[i].x = hp[i].x;
-        peaks[i].y = hp[i].y;
-        peaks[i].z = hp[i].z;
-        peaks[i].intensity = hp[i].intensity;
-        peaks[i].is_min = hp[i].is_min;
-        peaks[i].is_max = hp[i].is_max;
-    }
+    peaks_to_host(r, peaks, max_peaks, npeaks, sh.s);
 }
 
 // candidates -> interest points on the device: Localization.noLocalization (:19-45)
@@ -2033,9 +1995,49 @@ __global__ void k_to_points(const PeakOut* __restrict__ pk, const LocOut* __rest
     ips[i] = ip;
 }
 
-// ProcessDOG.compute's result: interest points after Localization (:150-168).  The
-// candidates (threshold / 10 with quadratic localisation: millions on a noisy 768^3
-// view) stay on the device; only the interest points are copied out.
+// The candidates (threshold / 10 with the DoG's quadratic localisation: millions on a
+// noisy 768^3 view) stay on the device; only the interest points are copied out.
+void points_from_peaks(DogWork& w, const DogRun& r, int localization, float keep_thr, spim_interest_point* out,
+                       int64_t max_out, int64_t* nout, hipStream_t s) {
+    const int64_t np = r.np;
+    int64_t n = 0;
+    const spim_interest_point* res = nullptr;
+    if (np > 0) {
+        grow(w.ips, size_t(np));
+        const unsigned grid = unsigned(ceil_div(np, int64_t(256)));
+        if (localization == 0) {
+            hipLaunchKernelGGL(k_to_points<false>, dim3(grid), dim3(256), 0, s, r.dpeaks, nullptr, np, 0.0f,
+                               w.ips.p, nullptr);
+            SD_HIP(hipGetLastError());
+            res = w.ips.p;
+            n = np;
+        } else {
+            grow(w.loc, size_t(np));
+            grow(w.flags, size_t(np));
+            grow(w.ips_sel, size_t(np));
+            grow(w.nsel, 1);
+            hipLaunchKernelGGL(k_localize, dim3(grid), dim3(256), 0, s, r.dog, r.d, r.dpeaks, np, w.loc.p);
+            SD_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_to_points<true>, dim3(grid), dim3(256), 0, s, r.dpeaks, w.loc.p, np, keep_thr,
+                               w.ips.p, w.flags.p);
+            SD_HIP(hipGetLastError());
+            const size_t tb = point_select_temp_bytes(np);
+            grow(w.sel_tmp, std::max<size_t>(tb, 1));
+            point_select(w.sel_tmp.p, tb, w.ips.p, w.flags.p, w.ips_sel.p, w.nsel.p, np, s);
+            int hn = 0;
+            SD_HIP(hipMemcpyAsync(&hn, w.nsel.p, sizeof(int), hipMemcpyDeviceToHost, s));
+            SD_HIP(hipStreamSynchronize(s));
+            res = w.ips_sel.p;
+            n = hn;
+        }
+    }
+    const int64_t m = out ? std::min<int64_t>(max_out, n) : 0;
+    if (m > 0) SD_HIP(hipMemcpyAsync(out, res, size_t(m) * sizeof(spim_interest_point), hipMemcpyDefault, s));
+    SD_HIP(hipStreamSynchronize(s));
+    *nout = n;
+}
+
+// ProcessDOG.compute's result: interest points after Localization (:150-168).
 void dog_interest_points(const float* img, const int64_t* dims, const spim_dog_params* p, int32_t extension,
                          float* dog_out, spim_interest_point* out, int64_t max_out, int64_t* nout) {
     SD_CHECK(nout && p, SPIMDECON_ERR_ARG, "null argument");
@@ -2047,42 +2049,7 @@ void dog_interest_points(const float* img, const int64_t* dims, const spim_dog_p
     StreamHolder sh(w);
     DogRun r;
     dog_run(img, dims, p, oob, dog_out, p->localization == 1 || dog_out != nullptr, sh.s, w, r);
-    const int64_t np = r.np;
-    int64_t n = 0;
-    const spim_interest_point* res = nullptr;
-    if (np > 0) {
-        grow(w.ips, size_t(np));
-        const unsigned grid = unsigned(ceil_div(np, int64_t(256)));
-        if (p->localization == 0) {
-            hipLaunchKernelGGL(k_to_points<false>, dim3(grid), dim3(256), 0, sh.s, r.dpeaks, nullptr, np, 0.0f,
-                               w.ips.p, nullptr);
-            SD_HIP(hipGetLastError());
-            res = w.ips.p;
-            n = np;
-        } else {
-            grow(w.loc, size_t(np));
-            grow(w.flags, size_t(np));
-            grow(w.ips_sel, size_t(np));
-            grow(w.nsel, 1);
-            hipLaunchKernelGGL(k_localize, dim3(grid), dim3(256), 0, sh.s, r.dog, r.d, r.dpeaks, np, w.loc.p);
-            SD_HIP(hipGetLastError());
-            hipLaunchKernelGGL(k_to_points<true>, dim3(grid), dim3(256), 0, sh.s, r.dpeaks, w.loc.p, np,
-                               float(p->threshold), w.ips.p, w.flags.p);
-            SD_HIP(hipGetLastError());
-            const size_t tb = point_select_temp_bytes(np);
-            grow(w.sel_tmp, std::max<size_t>(tb, 1));
-            point_select(w.sel_tmp.p, tb, w.ips.p, w.flags.p, w.ips_sel.p, w.nsel.p, np, sh.s);
-            int hn = 0;
-            SD_HIP(hipMemcpyAsync(&hn, w.nsel.p, sizeof(int), hipMemcpyDeviceToHost, sh.s));
-            SD_HIP(hipStreamSynchronize(sh.s));
-            res = w.ips_sel.p;
-            n = hn;
-        }
-    }
-    const int64_t m = out ? std::min<int64_t>(max_out, n) : 0;
-    if (m > 0) SD_HIP(hipMemcpyAsync(out, res, size_t(m) * sizeof(spim_interest_point), hipMemcpyDefault, sh.s));
-    SD_HIP(hipStreamSynchronize(sh.s));
-    *nout = n;
+    points_from_peaks(w, r, p->localization, float(p->threshold), out, max_out, nout, sh.s);
 }
 
 void dog_release_workspace(int dev) {

@@ -32,7 +32,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from . import _lib, dog, input_prep, psf as psf_mod
+from . import _lib, dog, dom, input_prep, psf as psf_mod
 from .decon import PSFTYPE, Session
 
 
@@ -105,12 +105,17 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
                       blending_border=(-8, -8, -8), blending_range=(12, 12, 12),
                       weight_type=input_prep.WeightType.VIRTUAL_WEIGHTS, device: int = 0,
                       log=None, digest: bool = False, refine: str | None = None,
-                      dog_extension: str = "mirror") -> TimepointResult:
+                      dog_extension: str = "mirror", detector: str = "dog", radius1: int = 2,
+                      radius2: int = 3) -> TimepointResult:
     """views: per view a [z, y, x] float32 torch tensor on the GPU (the acquired
     stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z);
     dog_extension: the detect stage's 'mirror' (accurate) or 'border' (approximate) GPU
-    mode (``dog.compute``)."""
+    mode (``dog.compute``); detector: 'dog' (Difference-of-Gaussian: sigma) or 'dom'
+    (Difference-of-Mean: radius1 / radius2, ``dom.compute``), both with threshold and
+    localization."""
     import torch
+    if detector not in ("dog", "dom"):
+        raise ValueError(f"detector must be 'dog' or 'dom', not {detector!r}")
     ms = {}
 
     def lap(name, t0):
@@ -123,9 +128,13 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
     torch.cuda.synchronize(device)
     t = time.perf_counter()
     points = []
-    for v in views:          # 1. ProcessDOG per view, read in place
-        pos, _ = dog.interest_points_array(v, sigma=sigma, threshold=threshold, localization=localization,
-                                           device=device, extension=dog_extension)
+    for v in views:          # 1. ProcessDOG (or ProcessDOM) per view, read in place
+        if detector == "dom":
+            pos, _ = dom.interest_points_array(v, radius1=radius1, radius2=radius2, threshold=threshold,
+                                               localization=localization, device=device)
+        else:
+            pos, _ = dog.interest_points_array(v, sigma=sigma, threshold=threshold, localization=localization,
+                                               device=device, extension=dog_extension)
         points.append(pos)
     t = lap("detect", t)
     gres = None
