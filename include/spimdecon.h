@@ -412,6 +412,53 @@ int spim_dom_interest_points(const float* img, const int64_t* dims, const spim_d
                              int64_t* nout);
 
 /* ======================================================================
+ * 6c. Descriptor-based pairwise registration, candidate stage: "redundant geometric local
+ *     descriptor matching" (translation invariant) --
+ *     spim/process/interestpointregistration/geometricdescriptor/RGLDMMatcher.java:44-123,
+ *     RGLDMPairwise.java:34-77, mpicbg/pointdescriptor/{AbstractPointDescriptor,
+ *     SimplePointDescriptor}.java, matcher/SubsetMatcher.java, similarity/SquareDistance.java.
+ *     Points are (n, 3) doubles (x, y, z), already mapped by the views' current models;
+ *     host or device pointers (as spim_dom_*).  Bit-exact against the reference's
+ *     arithmetic; the order of equal float distances in the neighbour search is this
+ *     library's (lower index first: the reference's kd-tree is not in its tree).
+ * ====================================================================== */
+typedef struct spim_rgldm_params {
+    int32_t num_neighbors;        /* 3   RGLDMParameters.numNeighbors          */
+    int32_t redundancy;           /* 1   RGLDMParameters.redundancy            */
+    float   ratio_of_distance;    /* 3   (float in the reference, widened to double at use) */
+    float   difference_threshold; /* 50                                        */
+    int32_t b_split;              /* 0 = auto; >0 forces that many partitions of B (tests) */
+    int32_t device;
+} spim_rgldm_params;
+
+void spim_rgldm_params_default(spim_rgldm_params* p);
+
+/* The matching kernel's tile sizes: A descriptors per block, B descriptors per LDS tile
+ * (the sizes at which its code takes another path).  Host only: needs no GPU. */
+void spim_rgldm_tiles(int32_t* a_tile, int32_t* b_tile);
+
+/* Per point its num_neighbors + redundancy nearest other points in ascending
+ * Detection.distanceTo (float) order -- neighbors[n * (nn+re)] -- and neighbour minus basis
+ * in double -- rel[n * (nn+re) * 3].  1 <= num_neighbors, 0 <= redundancy, nn + re <= 6;
+ * n >= nn + re + 1; coordinates finite (also as float); n <= 2^31 - 1: else
+ * SPIMDECON_ERR_ARG. */
+int spim_rgldm_descriptors(const double* pts, int64_t n, const spim_rgldm_params* p,
+                           int32_t* neighbors, double* rel);
+
+/* For every A descriptor over all B descriptors: best = the smallest descriptor distance
+ * (min over SubsetMatcher's pairings of the summed square distances / 3.0), best_idx the
+ * lowest B index attaining it, second = the second smallest of the multiset (from
+ * Double.MAX_VALUE down, best_idx -1 when nothing is below it).  Candidate i -> best_idx[i]
+ * is emitted in ascending A order when best < (double) difference_threshold &&
+ * best * (double) ratio_of_distance < second.  *count = the number of candidates; more
+ * than cap is SPIMDECON_ERR_ARG with *count still the needed size (best_idx / best /
+ * second are written all the same).  na or nb < nn + re + 1: no candidates, status OK
+ * ("Not enough detections to match").  The result does not depend on b_split. */
+int spim_rgldm_match(const double* a, int64_t na, const double* b, int64_t nb,
+                     const spim_rgldm_params* p, int32_t* best_idx, double* best, double* second,
+                     int32_t* cand_a, int32_t* cand_b, int64_t cap, int64_t* count);
+
+/* ======================================================================
  * 7. Deconvolution input preparation --
  *    spim/process/fusion/deconvolution/ProcessForDeconvolution.java:159-384:
  *    each view resampled into the fused bounding box through the inverse of

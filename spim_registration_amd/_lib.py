@@ -75,6 +75,17 @@ class DomParams(C.Structure):
     ]
 
 
+class RgldmParams(C.Structure):
+    _fields_ = [
+        ("num_neighbors", C.c_int32),
+        ("redundancy", C.c_int32),
+        ("ratio_of_distance", C.c_float),
+        ("difference_threshold", C.c_float),
+        ("b_split", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class Peak(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32),
                 ("intensity", C.c_float), ("is_min", C.c_int32), ("is_max", C.c_int32)]
@@ -164,6 +175,11 @@ SIGNATURES = {
     "spim_dom_compute": (C.c_int, [_pf, _pi64, C.POINTER(DomParams), _pf, C.POINTER(Peak), _i64, _pi64]),
     "spim_dom_interest_points": (C.c_int, [_pf, _pi64, C.POINTER(DomParams), _pf,
                                            C.POINTER(InterestPointC), _i64, _pi64]),
+    "spim_rgldm_params_default": (None, [C.POINTER(RgldmParams)]),
+    "spim_rgldm_tiles": (None, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "spim_rgldm_descriptors": (C.c_int, [C.c_void_p, _i64, C.POINTER(RgldmParams), C.c_void_p, C.c_void_p]),
+    "spim_rgldm_match": (C.c_int, [C.c_void_p, _i64, C.c_void_p, _i64, C.POINTER(RgldmParams), C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i64, _pi64]),
     "spim_psf_release_workspace": (C.c_int, [C.c_int]),
     "spim_save_interest_points": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(InterestPointC),
                                             C.POINTER(C.c_int32), C.c_int64]),

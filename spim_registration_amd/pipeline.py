@@ -4,14 +4,18 @@ The Fiji workflow the reference runs per timepoint, restated over this library:
 
   1. Detect Interest Points   ProcessDOG.compute per view (spim/process/interestpointdetection/
                               ProcessDOG.java:40-178) -> bead positions in view pixels
-  2. Register                 the view models are given (descriptor matching stays out of
-                              scope); the correspondences the registration would
-                              record are recovered from them (a detection corresponds when
-                              another view detected a bead within ``radius`` world pixels of
-                              it).  With ``refine`` = "translation" / "rigid" / "affine" the
-                              given models are first refined on the host: mutual nearest
-                              detections -> GlobalOpt.compute (globalopt.py, GlobalOpt.java:
-                              44-135), view 0 fixed
+  2. Register                 the view models are given; the correspondences the
+                              registration would record are recovered from them (a detection
+                              corresponds when another view detected a bead within ``radius``
+                              world pixels of it).  With ``refine`` = "translation" / "rigid" /
+                              "affine" the given models are first refined: pairwise matches
+                              -> GlobalOpt.compute (globalopt.py, GlobalOpt.java:44-135),
+                              view 0 fixed.  ``matching`` = "nearest" (the default) takes
+                              mutual nearest detections within ``radius`` (the models must
+                              already be right to that); "rgldm" runs the reference's
+                              descriptor matching (RGLDMPairwise.java:34-77: candidates on
+                              the GPU, RANSAC on the host; registration.py), which needs
+                              only approximate models
   3. Input preparation        ProcessForDeconvolution.fuseStacksAndGetPSFs (:159-384): views
                               resampled into the bounding box, blending weights normalised,
                               and per view the PSF extracted from its corresponding beads
@@ -106,16 +110,25 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
                       weight_type=input_prep.WeightType.VIRTUAL_WEIGHTS, device: int = 0,
                       log=None, digest: bool = False, refine: str | None = None,
                       dog_extension: str = "mirror", detector: str = "dog", radius1: int = 2,
-                      radius2: int = 3) -> TimepointResult:
+                      radius2: int = 3, matching: str = "nearest", num_neighbors: int = 3,
+                      redundancy: int = 1, ratio_of_distance: float = 3.0,
+                      difference_threshold: float = 50.0, max_epsilon: float = 5.0,
+                      min_inlier_ratio: float = 0.1, min_inlier_factor: float = 3.0,
+                      num_iterations: int = 1000, ransac_seed: int | None = None) -> TimepointResult:
     """views: per view a [z, y, x] float32 torch tensor on the GPU (the acquired
     stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z);
     dog_extension: the detect stage's 'mirror' (accurate) or 'border' (approximate) GPU
     mode (``dog.compute``); detector: 'dog' (Difference-of-Gaussian: sigma) or 'dom'
     (Difference-of-Mean: radius1 / radius2, ``dom.compute``), both with threshold and
-    localization."""
+    localization; matching (used when ``refine`` is set): 'nearest' or 'rgldm' with the
+    RGLDM (num_neighbors, redundancy, ratio_of_distance, difference_threshold) and RANSAC
+    (max_epsilon, min_inlier_ratio, min_inlier_factor, num_iterations, ransac_seed)
+    parameters of ``registration.pairwise_rgldm``."""
     import torch
     if detector not in ("dog", "dom"):
         raise ValueError(f"detector must be 'dog' or 'dom', not {detector!r}")
+    if matching not in ("nearest", "rgldm"):
+        raise ValueError(f"matching must be 'nearest' or 'rgldm', not {matching!r}")
     ms = {}
 
     def lap(name, t0):
@@ -139,10 +152,19 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
     t = lap("detect", t)
     gres = None
     models = [np.asarray(m, np.float64).reshape(3, 4) for m in models]
-    if refine is not None:   # 2'. GlobalOpt over mutual-nearest detections (host)
+    if refine is not None:   # 2'. GlobalOpt over pairwise matches (host)
         from . import globalopt
-        gres = globalopt.compute(len(models), globalopt.correspondences(points, models, radius),
-                                 model=refine, fixed=(0,))
+        if matching == "rgldm":   # RGLDM candidates on the views' device, RANSAC on the host
+            from . import registration
+            seed = registration.RANSAC_SEED if ransac_seed is None else ransac_seed
+            matches = registration.pairwise_rgldm(
+                points, models, model=refine, num_neighbors=num_neighbors, redundancy=redundancy,
+                ratio_of_distance=ratio_of_distance, difference_threshold=difference_threshold,
+                max_epsilon=max_epsilon, min_inlier_ratio=min_inlier_ratio, min_inlier_factor=min_inlier_factor,
+                num_iterations=num_iterations, seed=seed, device=device)
+        else:
+            matches = globalopt.correspondences(points, models, radius)
+        gres = globalopt.compute(len(models), matches, model=refine, fixed=(0,))
         if gres is not None:   # (a caught fit failure keeps the tiles' models as they stand, as the reference)
             if gres.failure and log:
                 log(gres.failure)

@@ -1,0 +1,222 @@
+"""Descriptor-based pairwise registration: RGLDM candidates on the GPU, RANSAC and the
+global optimisation on the host.
+
+The reference's default matcher when only detections and approximate view models are known
+is the "redundant geometric local descriptor matching" (translation invariant):
+
+  spim/process/interestpointregistration/geometricdescriptor/RGLDMPairwise.java:34-77
+  .../geometricdescriptor/RGLDMMatcher.java:44-123, RGLDMParameters.java (3 / 1 / 3 / 50)
+  mpicbg/pointdescriptor/{AbstractPointDescriptor,SimplePointDescriptor}.java,
+  matcher/SubsetMatcher.java, similarity/SquareDistance.java
+
+Every point is described by the vectors to its ``num_neighbors + redundancy`` nearest
+neighbours; two descriptors are compared over every pair of ``num_neighbors``-subsets, and a
+point of A is a candidate when its best B descriptor is below ``difference_threshold`` and
+``ratio_of_distance`` times better than the second best.  ``rgldm_candidates`` /
+``descriptors`` run that on the GPU (``spim_rgldm_match`` / ``spim_rgldm_descriptors``,
+csrc/rgldm.hip), bit-exact against the reference's arithmetic; there is no CPU path.  The
+order of neighbours at exactly the same float distance is unpinned (lower index first here;
+the reference's fiji.util.KDTree is not in its tree).
+
+``ransac`` restates ``RANSAC.computeRANSAC`` (spim/process/interestpointregistration/
+RANSAC.java:21-110) over mpicbg's ``Model.filterRansac`` on the host, in NumPy, with the
+model fits of ``globalopt.fit``.  Parity unpinned: mpicbg is not in the reference tree, so
+``filterRansac`` is restated from its published algorithm --
+
+  * ransac: ``num_iterations`` times draw a minimal sample of distinct candidates (index
+    ``int(u * n)``, redrawn while already chosen), fit, take the candidates closer than
+    ``max_epsilon`` as inliers, and refit on them while their number grows; a hypothesis is
+    good when it has at least the model's minimum of inliers and an inlier ratio above
+    ``min_inlier_ratio``; the good hypothesis with the strictly largest ratio is kept
+  * filter (maxTrust 4): refit on the kept set, drop matches farther than 4 x the median
+    distance, until none is dropped; the cost is the mean distance of the last fit
+
+-- and its random draws cannot match Java's.  The generator is NumPy's
+``Generator(PCG64(seed))`` and ``u = generator.random()``; the result is deterministic for a
+given seed.  Regularised models (``InterpolatedAffineModel3D``) are out of scope: ``model``
+is "translation", "rigid" or "affine".  RANSAC stays on the host on purpose: 10^3
+hypotheses over a few thousand candidates take milliseconds.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib, globalopt
+from ._lib import check
+
+__all__ = ["rgldm_candidates", "descriptors", "ransac", "pairwise_rgldm", "register", "tile_sizes"]
+
+RANSAC_SEED = 4711
+
+
+def _params(lib, num_neighbors, redundancy, ratio_of_distance, difference_threshold, device, b_split=0):
+    p = _lib.RgldmParams()
+    lib.spim_rgldm_params_default(C.byref(p))
+    p.num_neighbors, p.redundancy = int(num_neighbors), int(redundancy)
+    p.ratio_of_distance, p.difference_threshold = float(ratio_of_distance), float(difference_threshold)
+    p.b_split, p.device = int(b_split), int(device)
+    return p
+
+
+def _points(x):
+    """(pointer, n, the object that owns the memory) of an (n, 3) double array: a numpy array
+    or a CUDA torch tensor (read in place)."""
+    if hasattr(x, "is_cuda") and x.is_cuda:
+        import torch
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise ValueError("points must be (n, 3)")
+        x = x.contiguous().double()
+        torch.cuda.synchronize(x.device)   # the library runs on its own stream
+        return C.c_void_p(x.data_ptr()), int(x.shape[0]), x
+    a = np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1, 3))
+    return C.c_void_p(a.ctypes.data), len(a), a
+
+
+def tile_sizes():
+    """(A descriptors per block, B descriptors per LDS tile) of the matching kernel."""
+    a, b = C.c_int32(0), C.c_int32(0)
+    _lib.load().spim_rgldm_tiles(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
+
+
+def descriptors(points, num_neighbors: int = 3, redundancy: int = 1, device: int = 0):
+    """createSimplePointDescriptors: (neighbors (n, nn+re) int32 -- the nearest other points
+    in ascending float distance --, rel (n, nn+re, 3) float64 -- neighbour minus basis)."""
+    lib = _lib.load()
+    p = _params(lib, num_neighbors, redundancy, 3.0, 50.0, device)
+    ptr, n, _keep = _points(points)
+    m = max(int(num_neighbors) + int(redundancy), 0)
+    nbr = np.empty((n, m), np.int32)
+    rel = np.empty((n, m, 3), np.float64)
+    check(lib.spim_rgldm_descriptors(ptr, n, C.byref(p), C.c_void_p(nbr.ctypes.data), C.c_void_p(rel.ctypes.data)))
+    return nbr, rel
+
+
+def rgldm_candidates(pa, pb, num_neighbors: int = 3, redundancy: int = 1, ratio_of_distance: float = 3.0,
+                     difference_threshold: float = 50.0, device: int = 0, return_all: bool = False,
+                     b_split: int = 0):
+    """RGLDMMatcher.extractCorrespondenceCandidates over two (n, 3) point lists (numpy arrays
+    or CUDA torch tensors, x, y, z in one common frame): (ia, ib), candidate k pairs
+    pa[ia[k]] with pb[ib[k]], in ascending ia; with ``return_all`` also best_idx, best and
+    second over every point of pa.  ``b_split`` forces the partitions of B (0 = auto; the
+    result does not depend on it)."""
+    lib = _lib.load()
+    p = _params(lib, num_neighbors, redundancy, ratio_of_distance, difference_threshold, device, b_split)
+    aptr, na, _ka = _points(pa)
+    bptr, nb, _kb = _points(pb)
+    idx, best, second = np.empty(na, np.int32), np.empty(na, np.float64), np.empty(na, np.float64)
+    ia, ib = np.empty(max(na, 1), np.int32), np.empty(max(na, 1), np.int32)   # at most one candidate per A point
+    n = C.c_int64(0)
+    check(lib.spim_rgldm_match(aptr, na, bptr, nb, C.byref(p), C.c_void_p(idx.ctypes.data),
+                               C.c_void_p(best.ctypes.data), C.c_void_p(second.ctypes.data),
+                               C.c_void_p(ia.ctypes.data), C.c_void_p(ib.ctypes.data), na, C.byref(n)))
+    ia, ib = ia[:n.value].copy(), ib[:n.value].copy()
+    return (ia, ib, idx, best, second) if return_all else (ia, ib)
+
+
+def _inliers(kind, pa, pb, sel, eps):
+    """(model fitted to the matches sel, the candidates closer than eps under it)"""
+    m = globalopt.fit(kind, pa[sel], pb[sel], np.ones(len(sel)))
+    d = np.linalg.norm(globalopt.apply(m, pa) - pb, axis=1)
+    return m, np.nonzero(d < eps)[0]
+
+
+def ransac(pa, pb, model: str = "affine", max_epsilon: float = 5.0, min_inlier_ratio: float = 0.1,
+           min_inlier_factor: float = 3.0, num_iterations: int = 1000, seed: int = RANSAC_SEED):
+    """RANSAC.computeRANSAC over the candidates pa[i] <-> pb[i]: (inlier indices, the 3x4
+    model pa -> pb refitted on them, its mean error ``model.getCost()``); with too few
+    candidates, no model or too few inliers ((0,) indices, None, NaN)."""
+    if model not in globalopt.MIN_MATCHES:
+        raise ValueError(f"model must be one of {sorted(globalopt.MIN_MATCHES)}")
+    pa = np.asarray(pa, np.float64).reshape(-1, 3)
+    pb = np.asarray(pb, np.float64).reshape(-1, 3)
+    if len(pa) != len(pb):
+        raise ValueError("ransac needs as many points in pa as in pb")
+    none = (np.zeros(0, np.int64), None, float("nan"))
+    n, least = len(pa), globalopt.MIN_MATCHES[model]
+    # Math.round = floor(x + 0.5) (RANSAC.java:31)
+    min_num = max(least, int(np.floor(least * float(min_inlier_factor) + 0.5)))
+    if n < min_num:
+        return none
+    rng = np.random.Generator(np.random.PCG64(seed))
+    best_set, best_ratio = None, 0.0
+    for _ in range(int(num_iterations)):
+        sample = []
+        while len(sample) < least:
+            j = int(rng.random() * n)
+            if j not in sample:
+                sample.append(j)
+        try:
+            _, inl = _inliers(model, pa, pb, np.asarray(sample), max_epsilon)
+            good = len(inl) >= least and len(inl) / n > min_inlier_ratio
+            grown = 0
+            while good and grown < len(inl):
+                grown = len(inl)
+                _, inl = _inliers(model, pa, pb, inl, max_epsilon)
+                good = len(inl) >= least and len(inl) / n > min_inlier_ratio
+        except globalopt.IllDefinedDataPoints:
+            continue
+        if good and len(inl) / n > best_ratio:
+            best_set, best_ratio = inl, len(inl) / n
+    if best_set is None:
+        return none
+    # Model.filter, maxTrust 4: the median-based filter
+    inl = best_set
+    while True:
+        try:
+            m = globalopt.fit(model, pa[inl], pb[inl], np.ones(len(inl)))
+        except (globalopt.NotEnoughDataPoints, globalopt.IllDefinedDataPoints):
+            return none
+        d = np.linalg.norm(globalopt.apply(m, pa[inl]) - pb[inl], axis=1)
+        cost = float(d.mean())
+        kept = inl[d <= float(np.median(d)) * 4.0]
+        if len(kept) == len(inl):
+            break
+        inl = kept
+    if len(inl) < max(least, min_num):
+        return none
+    return inl, m, cost
+
+
+def pairwise_rgldm(points, models, pairs=None, model: str = "affine", num_neighbors: int = 3, redundancy: int = 1,
+                   ratio_of_distance: float = 3.0, difference_threshold: float = 50.0, max_epsilon: float = 5.0,
+                   min_inlier_ratio: float = 0.1, min_inlier_factor: float = 3.0, num_iterations: int = 1000,
+                   seed: int = RANSAC_SEED, device: int = 0, candidates=None):
+    """RGLDMPairwise.call over all view pairs (or ``pairs``, (a, b) tuples): the views'
+    detections mapped by their current ``models`` (GlobalOptimizationType.java:208-213), the
+    RGLDM candidates on GPU ``device``, RANSAC on the host.  Returns the pairs with inliers
+    as ``globalopt.PairwiseMatch`` over world points under ``models``.  ``candidates``: a
+    callable (pa, pb, **rgldm parameters) -> (ia, ib) to use in place of the GPU matcher
+    (the tests feed the restatement's candidates through the same code)."""
+    world = [globalopt.apply(np.asarray(m, np.float64).reshape(3, 4), np.asarray(p, np.float64).reshape(-1, 3))
+             for p, m in zip(points, models)]
+    if pairs is None:
+        pairs = [(a, b) for a in range(len(world)) for b in range(a + 1, len(world))]
+    kw = dict(num_neighbors=num_neighbors, redundancy=redundancy, ratio_of_distance=ratio_of_distance,
+              difference_threshold=difference_threshold)
+    out = []
+    for a, b in pairs:
+        if candidates is None:
+            ia, ib = rgldm_candidates(world[a], world[b], device=device, **kw)
+        else:
+            ia, ib = candidates(world[a], world[b], **kw)
+        ca, cb = world[a][ia], world[b][ib]
+        inl, _, _ = ransac(ca, cb, model, max_epsilon, min_inlier_ratio, min_inlier_factor, num_iterations, seed)
+        if len(inl):
+            out.append(globalopt.PairwiseMatch(a, b, ca[inl], cb[inl]))
+    return out
+
+
+def register(points, models, model: str = "affine", fixed=(0,), **kw):
+    """Descriptor-based registration of the views from their detections and approximate
+    models: ``pairwise_rgldm`` (its keywords pass through), ``globalopt.compute`` and
+    ``globalopt.concatenate``.  Returns (the refined 3x4 models, the GlobalOptResult -- None
+    when no pair has inliers, the models then are the given ones)."""
+    models = [np.asarray(m, np.float64).reshape(3, 4) for m in models]
+    matches = pairwise_rgldm(points, models, model=model, **kw)
+    res = globalopt.compute(len(models), matches, model=model, fixed=fixed)
+    if res is not None:
+        models = [globalopt.concatenate(c, m) for c, m in zip(res.models, models)]
+    return models, res
