@@ -640,6 +640,13 @@ int  lrsim_run(lrsim_session* h, int iters, int multiplicative, double lambda, d
 int  lrsim_get_psi(lrsim_session* h, float* out);
 /* padded FFT lengths {Mx, My, Mz} (info) */
 int  lrsim_fft_dims(lrsim_session* h, int64_t* out3);
+/* The per-voxel rule of lrsim_run alone (:254-330; tests): psi_out = rule(psi_in, value,
+ * num), Tikhonov for lambda > 0, the NaN / minValue clamp; stats2 (host) receives
+ * {sumChange, maxChange}.  psi_in, value, num, psi_out: n >= 1 voxels in device memory of
+ * the current device (psi_out may be psi_in).  Same kernel, launch geometry and reduction
+ * as an iteration of lrsim_run. */
+int  lrsim_update_rule(const float* psi_in, const double* value, const double* num, int64_t n,
+                       int multiplicative, double lambda, float* psi_out, double* stats2);
 
 #ifdef __cplusplus
 }

@@ -213,6 +213,8 @@ SIGNATURES = {
     "lrsim_run": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, _pd]),
     "lrsim_get_psi": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lrsim_fft_dims": (C.c_int, [C.c_void_p, _pi64]),
+    "lrsim_update_rule": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_double,
+                                    C.c_void_p, _pd]),
     "spim_prepare_inputs": (C.c_int, [C.c_int, C.POINTER(ViewSource), C.POINTER(InputParams),
                                       C.POINTER(_pf), C.POINTER(_pf), C.POINTER(C.c_double),
                                       C.POINTER(C.c_int), C.POINTER(C.c_double)]),

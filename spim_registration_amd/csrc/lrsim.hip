@@ -300,6 +300,23 @@ __global__ __launch_bounds__(1024) void k_lr_sum2(const double* __restrict__ par
     }
 }
 
+// the rule's four variants by (multiplicative, lambda > 0); `part`: two doubles per block
+void launch_lr_update(int64_t n, float* psi, const double* value, const double* num, bool mult, double lambda,
+                      double* part, hipStream_t st) {
+    const unsigned gb = grid_of(n, kB);
+    auto upd = [&](auto m, auto t) {
+        hipLaunchKernelGGL((k_lr_update<decltype(m)::value, decltype(t)::value>), dim3(gb), dim3(kB), 0, st, n, psi,
+                           value, num, lambda, part);
+    };
+    using T = std::true_type;
+    using F = std::false_type;
+    if (mult && lambda > 0) upd(T{}, T{});
+    else if (mult) upd(T{}, F{});
+    else if (lambda > 0) upd(F{}, T{});
+    else upd(F{}, F{});
+    SD_HIP(hipGetLastError());
+}
+
 // a = a + b, or a * b (mult): one device group's partial merged into group 0's
 __global__ __launch_bounds__(kB) void k_lr_merge(double* __restrict__ a, const double* __restrict__ b, int64_t n,
                                                  int mult) {
@@ -308,6 +325,15 @@ __global__ __launch_bounds__(kB) void k_lr_merge(double* __restrict__ a, const d
 }
 
 }  // namespace
+
+// k_lr_update on the caller's device arrays (psi in place) with the launch geometry and the
+// partials' reduction of lrsim_run; part: 2 * min(ceil(n / 256), 4096) doubles, red: 2
+// (lrsim_update_rule: the rule under test, voxel by voxel)
+void lr_update_rule(int64_t n, float* psi, const double* value, const double* num, bool mult, double lambda,
+                    double* part, double* red) {
+    launch_lr_update(n, psi, value, num, mult, lambda, part, nullptr);
+    launch_reduce_partials(part, int64_t(grid_of(n, kB)), red, 0, nullptr);
+}
 
 // ---------------------------------------------------------------- the session
 
@@ -436,15 +462,17 @@ public:
         SD_CHECK(!inited_, SPIMDECON_ERR_STATE, "lrsim_init called twice");
         SD_CHECK(!views_.empty(), SPIMDECON_ERR_STATE, "no views");
         int c[3] = {0, 0, 0};
-        int64_t khash = 0;
+        uint64_t khash = 0;   // unsigned: wraps (defined) from the fourth view on
         for (auto& v : views_)
             for (int d = 0; d < 3; ++d) {
                 c[d] = std::max(c[d], v.kd[d] / 2);
-                khash = khash * 131 + v.kd[d];
+                khash = khash * 131u + uint64_t(v.kd[d]);
             }
         {
+            int64_t kh;
+            std::memcpy(&kh, &khash, 8);   // a bit copy: the field is only compared
             const int64_t mine[7] = {0x4c52534d31LL, nranks_, dims_[0], dims_[1], dims_[2], int64_t(views_.size()),
-                                     khash};
+                                     kh};
             agree(mine, 7, "lrsim_init");
         }
         g_.nx = dims_[0]; g_.ny = dims_[1]; g_.nz = dims_[2];
@@ -577,17 +605,7 @@ public:
             // (product / sum) over the ranks
             merge_groups(&LrGroup::value, mult);
             allreduce(G0.value.p, n_, mult ? ncclProd : ncclSum);
-            auto upd = [&](auto m, auto t) {
-                hipLaunchKernelGGL((k_lr_update<decltype(m)::value, decltype(t)::value>), dim3(gb), dim3(kB), 0,
-                                   G0.st, n_, G0.psi.p, G0.value.p, G0.num.p, lambda, part_.p);
-            };
-            using T = std::true_type;
-            using F = std::false_type;
-            if (mult && lambda > 0) upd(T{}, T{});
-            else if (mult) upd(T{}, F{});
-            else if (lambda > 0) upd(F{}, T{});
-            else upd(F{}, F{});
-            SD_HIP(hipGetLastError());
+            launch_lr_update(n_, G0.psi.p, G0.value.p, G0.num.p, mult, lambda, part_.p, G0.st);
             launch_reduce_partials(part_.p, int64_t(gb), red_.p, 0, G0.st);
             // the new psi to the other groups (on group 0's stream; they wait for it)
             for (size_t g = 1; g < grp_.size(); ++g)
@@ -799,6 +817,20 @@ int lrsim_run(lrsim_session* h, int iters, int multiplicative, double lambda, do
 
 int lrsim_get_psi(lrsim_session* h, float* out) {
     return guarded([&] { LRS(h); S.get_psi(out); });
+}
+
+int lrsim_update_rule(const float* psi_in, const double* value, const double* num, int64_t n, int multiplicative,
+                      double lambda, float* psi_out, double* stats2) {
+    return guarded([&] {
+        SD_CHECK(n >= 1, SPIMDECON_ERR_ARG, "n must be >= 1");
+        SD_CHECK(psi_in && value && num && psi_out && stats2, SPIMDECON_ERR_ARG, "null pointer");
+        const int64_t gb = std::min<int64_t>(spimdecon::ceil_div(n, int64_t(256)), 4096);   // grid_of(n, 256)
+        spimdecon::DBuf<double> part(size_t(2) * size_t(gb)), red(2);
+        if (psi_out != psi_in) SD_HIP(hipMemcpyAsync(psi_out, psi_in, size_t(n) * 4, hipMemcpyDeviceToDevice, nullptr));
+        spimdecon::lr_update_rule(n, psi_out, value, num, multiplicative != 0, lambda, part.p, red.p);
+        SD_HIP(hipMemcpyAsync(stats2, red.p, 16, hipMemcpyDeviceToHost, nullptr));
+        SD_HIP(hipStreamSynchronize(nullptr));
+    });
 }
 
 int lrsim_fft_dims(lrsim_session* h, int64_t* out3) {

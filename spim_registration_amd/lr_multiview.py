@@ -70,32 +70,52 @@ class LucyRichardsonMultiViewDeconvolution:
     @staticmethod
     def lucyRichardsonMultiView(data, minIterations, maxIterations, multiplicative, lambda_, numThreads,
                                 device: int = 0, nranks: int = 1, rank: int = 0, comm_id: bytes | None = None,
-                                stats_out: list | None = None, avg_out: list | None = None):
+                                stats_out: list | None = None, avg_out: list | None = None, shape=None,
+                                fft_dims_out: list | None = None):
         return lucy_richardson_multi_view(data, maxIterations, multiplicative, lambda_, device=device,
                                           nranks=nranks, rank=rank, comm_id=comm_id, stats_out=stats_out,
-                                          avg_out=avg_out)
+                                          avg_out=avg_out, shape=shape, fft_dims_out=fft_dims_out)
 
 
 def lucy_richardson_multi_view(data, max_iterations: int, multiplicative: bool, lambda_: float, device: int = 0,
                                nranks: int = 1, rank: int = 0, comm_id: bytes | None = None,
                                stats_out: list | None = None, avg_out: list | None = None,
-                               devices=None) -> np.ndarray:
+                               devices=None, shape=None, fft_dims_out: list | None = None) -> np.ndarray:
     """Runs LucyRichardsonMultiViewDeconvolution.lucyRichardsonMultiView (:24-358) and
     returns psi.  ``minIterations`` of the reference is unused there too; the do-while
     (:98-351) runs max(1, maxIterations) iterations.  ``stats_out`` receives
     (sumChange, maxChange) per iteration, ``avg_out`` the initial average (:63).
     ``devices``: several GPUs of this process (view v on devices[v % len]; ids may
-    repeat), as the reference's threads; not combined with RCCL ranks."""
+    repeat), as the reference's threads; not combined with RCCL ranks.
+    ``shape``: the volume's (z, y, x); required on a rank that owns no view (more ranks
+    than views), otherwise taken from the first owned image.  Every owned view is checked
+    against it, and the kernel dims for oddness, before the session (and with it the
+    communicator) is created: a bad rank fails before any collective.
+    ``fft_dims_out`` receives the padded transform lengths [Mx, My, Mz]."""
     if not data:
         raise ValueError("no views")
     lib = _lib.load()
-    dims = None
-    for v in data:
-        if v.image is not None:
-            dims = v.image.shape
-            break
+    dims = None if shape is None else tuple(int(s) for s in shape)
     if dims is None:
-        raise ValueError("at least one view must carry its image on every rank that owns one")
+        for i, v in enumerate(data):
+            if i % nranks == rank and v.image is not None:
+                dims = tuple(v.image.shape)
+                break
+    if dims is None:
+        raise ValueError("no owned view carries an image: a rank that owns no view needs shape=(z, y, x)")
+    if len(dims) != 3 or min(dims) < 1:
+        raise ValueError(f"shape must be a positive (z, y, x), got {dims}")
+    for i, v in enumerate(data):
+        if v.kernel.ndim != 3 or any(s % 2 == 0 for s in v.kernel.shape):
+            raise ValueError(f"view {i}: kernel dims must be odd, got {v.kernel.shape}")
+        if i % nranks != rank:
+            continue
+        for a, nm in ((v.image, "image"), (v.weight, "weight")):
+            if a is None:
+                raise ValueError(f"view {i} is owned by rank {rank} and needs its {nm} "
+                                 "(normAllImages reads every weight, :401)")
+            if a.shape != dims:
+                raise ValueError(f"view {i}: {nm} shape {a.shape} != {dims}")
     nz, ny, nx = dims
     d = (C.c_int64 * 3)(nx, ny, nz)
     h = C.c_void_p()
@@ -111,14 +131,7 @@ def lucy_richardson_multi_view(data, max_iterations: int, multiplicative: bool, 
         for i, v in enumerate(data):
             kz, ky, kx = v.kernel.shape
             kd = np.array([kx, ky, kz], np.int32)
-            mine = i % nranks == rank
-            if mine:
-                for a, nm in ((v.image, "image"), (v.weight, "weight")):
-                    if a is None:
-                        raise ValueError(f"view {i} is owned by rank {rank} and needs its {nm} "
-                                         "(normAllImages reads every weight, :401)")
-                    if a.shape != tuple(dims):
-                        raise ValueError(f"view {i}: {nm} shape {a.shape} != {tuple(dims)}")
+            if i % nranks == rank:
                 check(lib.lrsim_add_view(h, v.image.ctypes.data, v.weight.ctypes.data, v.kernel.ctypes.data,
                                          kd.ctypes.data_as(_lib._pi)))
             else:
@@ -127,6 +140,10 @@ def lucy_richardson_multi_view(data, max_iterations: int, multiplicative: bool, 
         check(lib.lrsim_init(h, C.byref(avg)))
         if avg_out is not None:
             avg_out.append(avg.value)
+        if fft_dims_out is not None:
+            m = (C.c_int64 * 3)()
+            check(lib.lrsim_fft_dims(h, m))
+            fft_dims_out.extend(int(x) for x in m)
         iters = max(1, int(max_iterations))
         st = np.zeros(2 * iters, np.float64)
         check(lib.lrsim_run(h, iters, 1 if multiplicative else 0, float(lambda_),

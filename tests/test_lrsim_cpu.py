@@ -173,3 +173,64 @@ def test_view_sharded_allreduce_gloo_world2(mult):
     assert ok[1] < 1e-6, ok     # view-sharded all-reduce == every view in one process
     assert ok[2] < 1e-5, ok     # statistics (identical on every rank)
     assert ok[3] < 1e-12, ok    # the initial average from the reduced overlap partials
+
+
+class _RecordingLib:
+    """Stands in for libspimdecon.so: records the lrsim_* calls, every one succeeds."""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        if not name.startswith("lrsim_"):
+            raise AttributeError(name)
+
+        def call(*args):
+            self.calls.append((name, args))
+            return 0
+        return call
+
+
+def test_rank_without_views_takes_the_shape_argument(monkeypatch):
+    """More ranks than views: rank 1 of 2 owns nothing of a single view.  With shape= it
+    reaches lrsim_create (where its peers wait in the communicator's initialisation) and
+    adds the view with null pointers; a wrong-shaped owned view, an even kernel or a
+    missing shape raise before lrsim_create, i.e. before any collective."""
+    from spim_registration_amd import _lib, lr_multiview as lm
+    rec = _RecordingLib()
+    monkeypatch.setattr(_lib, "load", lambda: rec)
+    view = lm.LucyRichardsonFFT(None, None, np.ones((3, 5, 7), np.float32))
+    dims_out = []
+    psi = lm.lucy_richardson_multi_view([view], 2, False, 0.0, nranks=2, rank=1, comm_id=b"\1" * 128,
+                                        shape=SHAPE, fft_dims_out=dims_out)
+    names = [c[0] for c in rec.calls]
+    assert names == ["lrsim_create", "lrsim_add_view", "lrsim_init", "lrsim_fft_dims", "lrsim_run",
+                     "lrsim_get_psi", "lrsim_destroy"]
+    create, add = rec.calls[0][1], rec.calls[1][1]
+    assert list(create[0]) == [SHAPE[2], SHAPE[1], SHAPE[0]] and create[2:4] == (2, 1)
+    assert add[1] is None and add[2] is None and add[3] is None
+    assert list(add[4][:3]) == [7, 5, 3]                      # the kernel dims travel on every rank
+    assert psi.shape == SHAPE and len(dims_out) == 3
+
+    def created(**kw):
+        rec.calls.clear()
+        with pytest.raises(ValueError):
+            lm.lucy_richardson_multi_view(**kw)
+        return any(c[0] == "lrsim_create" for c in rec.calls)
+
+    img = np.ones(SHAPE, np.float32)
+    good = lm.LucyRichardsonFFT(img, img, np.ones((3, 3, 3), np.float32))
+    bad = lm.LucyRichardsonFFT(img[1:], img[1:], np.ones((3, 3, 3), np.float32))
+    base = dict(max_iterations=1, multiplicative=False, lambda_=0.0)
+    assert not created(data=[view], nranks=2, rank=1, **base)                     # no shape, no owned view
+    assert not created(data=[good, bad], shape=SHAPE, **base)                     # owned view of another shape
+    assert not created(data=[bad, good], **base)                                  # ... against the first view's
+    assert not created(data=[good, good], shape=(SHAPE[0], SHAPE[1]), **base)
+    even = lm.LucyRichardsonFFT(img, img, np.ones((3, 3, 3), np.float32))
+    even.kernel = np.ones((3, 4, 3), np.float32)                                  # replaced after construction
+    assert not created(data=[good, even], nranks=2, rank=0, shape=SHAPE, **base)  # another rank's view, too
+    # a view of another rank may have any shape (it is not read) and a good call goes through
+    rec.calls.clear()
+    lm.lucy_richardson_multi_view([good, bad], 1, False, 0.0, nranks=2, rank=0, comm_id=b"\1" * 128)
+    assert [c[0] for c in rec.calls][:3] == ["lrsim_create", "lrsim_add_view", "lrsim_add_view"]
+    assert rec.calls[1][1][1] is not None and rec.calls[2][1][1] is None
