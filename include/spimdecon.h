@@ -459,6 +459,49 @@ int spim_rgldm_match(const double* a, int64_t na, const double* b, int64_t nb,
                      int32_t* cand_a, int32_t* cand_b, int64_t cap, int64_t* count);
 
 /* ======================================================================
+ * 6d. Pairwise registration, candidate stage: "fast 3d geometric hashing (rotation
+ *     invariant)" -- spim/process/interestpointregistration/geometrichashing/
+ *     GeometricHashingPairwise.java:45-86, GeometricHasher.java:54-116, mpicbg/pointdescriptor/
+ *     LocalCoordinateSystemPointDescriptor.java:37-175, spim/vecmath/{Vector3d,Matrix3d}.java.
+ *     Every point is described in the local coordinate system of its 3 nearest neighbours
+ *     (normalize = false: six floats ax bx by cx cy cz), so the view models need not be
+ *     rotationally right.  Points as in 6c.  Bit-exact against the reference's arithmetic;
+ *     the ranking of B descriptors is this library's (the reference's kd-tree is not in its
+ *     tree): by (float) Math.sqrt(descriptorDistance) ascending, equal floats by lower B
+ *     index, a NaN distance not ranked.
+ * ====================================================================== */
+typedef struct spim_gh_params {
+    double  ratio_of_distance;    /* 10  GeometricHashingParameters.ratioOfDistance     */
+    double  difference_threshold; /* 50  GeometricHashingParameters.differenceThreshold */
+    int32_t b_split;              /* 0 = auto; >0 forces that many partitions of B (tests) */
+    int32_t device;
+} spim_gh_params;
+
+void spim_gh_params_default(spim_gh_params* p);
+
+/* The matching kernel's tile sizes: A descriptors per block, B descriptors per LDS tile.
+ * Host only: needs no GPU. */
+void spim_gh_tiles(int32_t* a_tile, int32_t* b_tile);
+
+/* Per point its 3 nearest other points in ascending Detection.distanceTo (float) order, equal
+ * floats by lower index -- neighbors[n * 3] -- and its descriptor -- desc[n * 6]: ax bx by cx
+ * cy cz (a matrix without inverse leaves bx .. cz at 0, as the reference's catch).  n >= 4;
+ * coordinates finite (also as float); n <= 2^31 - 1: else SPIMDECON_ERR_ARG. */
+int spim_gh_descriptors(const double* pts, int64_t n, const spim_gh_params* p,
+                        int32_t* neighbors, float* desc);
+
+/* For every A descriptor the two first ranked B descriptors: best_idx the first, best and
+ * second their descriptorDistance (float differences and products, a double sum); with fewer
+ * than two ranked, Double.MAX_VALUE / Double.MAX_VALUE / -1 and no candidate.  Candidate
+ * i -> best_idx[i] is emitted in ascending A order when best < difference_threshold &&
+ * best * ratio_of_distance <= second.  *count, cap and the written outputs as
+ * spim_rgldm_match.  na or nb < 4: no candidates, status OK ("Not enough detections to
+ * match").  The result does not depend on b_split. */
+int spim_gh_match(const double* a, int64_t na, const double* b, int64_t nb,
+                  const spim_gh_params* p, int32_t* best_idx, double* best, double* second,
+                  int32_t* cand_a, int32_t* cand_b, int64_t cap, int64_t* count);
+
+/* ======================================================================
  * 7. Deconvolution input preparation --
  *    spim/process/fusion/deconvolution/ProcessForDeconvolution.java:159-384:
  *    each view resampled into the fused bounding box through the inverse of

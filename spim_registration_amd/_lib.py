@@ -86,6 +86,15 @@ class RgldmParams(C.Structure):
     ]
 
 
+class GhParams(C.Structure):
+    _fields_ = [
+        ("ratio_of_distance", C.c_double),
+        ("difference_threshold", C.c_double),
+        ("b_split", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class Peak(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32),
                 ("intensity", C.c_float), ("is_min", C.c_int32), ("is_max", C.c_int32)]
@@ -180,6 +189,11 @@ SIGNATURES = {
     "spim_rgldm_descriptors": (C.c_int, [C.c_void_p, _i64, C.POINTER(RgldmParams), C.c_void_p, C.c_void_p]),
     "spim_rgldm_match": (C.c_int, [C.c_void_p, _i64, C.c_void_p, _i64, C.POINTER(RgldmParams), C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i64, _pi64]),
+    "spim_gh_params_default": (None, [C.POINTER(GhParams)]),
+    "spim_gh_tiles": (None, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "spim_gh_descriptors": (C.c_int, [C.c_void_p, _i64, C.POINTER(GhParams), C.c_void_p, C.c_void_p]),
+    "spim_gh_match": (C.c_int, [C.c_void_p, _i64, C.c_void_p, _i64, C.POINTER(GhParams), C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i64, _pi64]),
     "spim_psf_release_workspace": (C.c_int, [C.c_int]),
     "spim_save_interest_points": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(InterestPointC),
                                             C.POINTER(C.c_int32), C.c_int64]),

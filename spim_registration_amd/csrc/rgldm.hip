@@ -34,6 +34,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "rgldm.hpp"
 
 namespace spimdecon {
 
@@ -338,22 +339,23 @@ void rg_check_points(const double* pts, int64_t n) {
 }
 
 // the points on the device (in place when they already are) and checked finite
-const double* rg_stage(const double* pts, int64_t n, int dev, DBuf<double>& buf, RgWork& w, hipStream_t s) {
+const double* rg_stage(const double* pts, int64_t n, int dev, DBuf<double>& buf, DBuf<int>& bad_buf, hipStream_t s,
+                       const char* who = "rgldm") {
     const double* d = pts;
     if (!is_device_ptr(pts, dev)) {
         rg_grow(buf, size_t(3 * n));
         SD_HIP(hipMemcpyAsync(buf.p, pts, size_t(3 * n) * sizeof(double), hipMemcpyDefault, s));
         d = buf.p;
     }
-    rg_grow(w.bad, 1);
-    SD_HIP(hipMemsetAsync(w.bad.p, 0, sizeof(int), s));
+    rg_grow(bad_buf, 1);
+    SD_HIP(hipMemsetAsync(bad_buf.p, 0, sizeof(int), s));
     const unsigned g = unsigned(std::min<int64_t>(ceil_div(3 * n, 256), 1024));
-    hipLaunchKernelGGL(k_rgldm_finite, dim3(g), dim3(256), 0, s, d, 3 * n, w.bad.p);
+    hipLaunchKernelGGL(k_rgldm_finite, dim3(g), dim3(256), 0, s, d, 3 * n, bad_buf.p);
     SD_HIP(hipGetLastError());
     int bad = 0;
-    SD_HIP(hipMemcpyAsync(&bad, w.bad.p, sizeof(int), hipMemcpyDeviceToHost, s));
+    SD_HIP(hipMemcpyAsync(&bad, bad_buf.p, sizeof(int), hipMemcpyDeviceToHost, s));
     SD_HIP(hipStreamSynchronize(s));
-    SD_CHECK(!bad, SPIMDECON_ERR_ARG, "rgldm: non-finite coordinates");
+    SD_CHECK(!bad, SPIMDECON_ERR_ARG, std::string(who) + ": non-finite coordinates");
     return d;
 }
 
@@ -395,7 +397,7 @@ void rgldm_descriptors(const double* pts, int64_t n, const spim_rgldm_params* p,
     RgWork& w = rg_work(p->device);
     std::lock_guard<std::mutex> lk(w.mu);
     hipStream_t s = w.get_stream();
-    const double* d = rg_stage(pts, n, p->device, w.pts_a, w, s);
+    const double* d = rg_stage(pts, n, p->device, w.pts_a, w.bad, s);
     rg_grow(w.nbr_a, size_t(n) * m);
     rg_grow(w.rel_a, size_t(n) * m * 3);
     rg_knn(d, int(n), m, w.nbr_a.p, w.rel_a.p, s);
@@ -418,8 +420,8 @@ void rgldm_match(const double* a, int64_t na, const double* b, int64_t nb, const
     RgWork& w = rg_work(p->device);
     std::lock_guard<std::mutex> lk(w.mu);
     hipStream_t s = w.get_stream();
-    const double* da = na ? rg_stage(a, na, p->device, w.pts_a, w, s) : nullptr;
-    const double* db = nb ? rg_stage(b, nb, p->device, w.pts_b, w, s) : nullptr;
+    const double* da = na ? rg_stage(a, na, p->device, w.pts_a, w.bad, s) : nullptr;
+    const double* db = nb ? rg_stage(b, nb, p->device, w.pts_b, w.bad, s) : nullptr;
     if (na == 0) return;
     rg_grow(w.best, size_t(na));
     rg_grow(w.second, size_t(na));
@@ -482,6 +484,24 @@ void rgldm_match(const double* a, int64_t na, const double* b, int64_t nb, const
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------- shared with geohash.hip (rgldm.hpp)
+const double* pm_stage_points(const double* pts, int64_t n, int dev, DBuf<double>& buf, DBuf<int>& bad,
+                              hipStream_t s, const char* who) {
+    rg_check_points(pts, n);
+    return rg_stage(pts, n, dev, buf, bad, s, who);
+}
+
+void pm_knn(const double* dpts, int n, int m, int* nbr, double* rel, hipStream_t s) {
+    rg_knn(dpts, n, m, nbr, rel, s);
+}
+
+void pm_compact(int na, const unsigned char* flag, const int* idx, int* cand_a, int* cand_b, int64_t cap,
+                int64_t* count, hipStream_t s) {
+    hipLaunchKernelGGL(k_rgldm_compact, dim3(1), dim3(kRgScanBlock), 0, s, na, flag, idx, cand_a, cand_b, cap, count);
+    SD_HIP(hipGetLastError());
+}
+
 }  // namespace spimdecon
 
 // ---------------------------------------------------------------- extern "C"

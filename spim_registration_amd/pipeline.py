@@ -15,7 +15,9 @@ The Fiji workflow the reference runs per timepoint, restated over this library:
                               already be right to that); "rgldm" runs the reference's
                               descriptor matching (RGLDMPairwise.java:34-77: candidates on
                               the GPU, RANSAC on the host; registration.py), which needs
-                              only approximate models
+                              only approximate models; "geometric_hashing" the rotation
+                              invariant matcher (GeometricHashingPairwise.java:45-86), which
+                              does not need their rotations either
   3. Input preparation        ProcessForDeconvolution.fuseStacksAndGetPSFs (:159-384): views
                               resampled into the bounding box, blending weights normalised,
                               and per view the PSF extracted from its corresponding beads
@@ -111,7 +113,7 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
                       log=None, digest: bool = False, refine: str | None = None,
                       dog_extension: str = "mirror", detector: str = "dog", radius1: int = 2,
                       radius2: int = 3, matching: str = "nearest", num_neighbors: int = 3,
-                      redundancy: int = 1, ratio_of_distance: float = 3.0,
+                      redundancy: int = 1, ratio_of_distance: float | None = None,
                       difference_threshold: float = 50.0, max_epsilon: float = 5.0,
                       min_inlier_ratio: float = 0.1, min_inlier_factor: float = 3.0,
                       num_iterations: int = 1000, ransac_seed: int | None = None) -> TimepointResult:
@@ -120,15 +122,18 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
     dog_extension: the detect stage's 'mirror' (accurate) or 'border' (approximate) GPU
     mode (``dog.compute``); detector: 'dog' (Difference-of-Gaussian: sigma) or 'dom'
     (Difference-of-Mean: radius1 / radius2, ``dom.compute``), both with threshold and
-    localization; matching (used when ``refine`` is set): 'nearest' or 'rgldm' with the
+    localization; matching (used when ``refine`` is set): 'nearest', 'rgldm' with the
     RGLDM (num_neighbors, redundancy, ratio_of_distance, difference_threshold) and RANSAC
     (max_epsilon, min_inlier_ratio, min_inlier_factor, num_iterations, ransac_seed)
-    parameters of ``registration.pairwise_rgldm``."""
+    parameters of ``registration.pairwise_rgldm``, or 'geometric_hashing' (rotation
+    invariant: ratio_of_distance, difference_threshold and the RANSAC parameters of
+    ``registration.pairwise_geometric_hashing``); ratio_of_distance None = the matcher's
+    default, 3 for RGLDM and 10 for geometric hashing."""
     import torch
     if detector not in ("dog", "dom"):
         raise ValueError(f"detector must be 'dog' or 'dom', not {detector!r}")
-    if matching not in ("nearest", "rgldm"):
-        raise ValueError(f"matching must be 'nearest' or 'rgldm', not {matching!r}")
+    if matching not in ("nearest", "rgldm", "geometric_hashing"):
+        raise ValueError(f"matching must be 'nearest', 'rgldm' or 'geometric_hashing', not {matching!r}")
     ms = {}
 
     def lap(name, t0):
@@ -159,7 +164,17 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
             seed = registration.RANSAC_SEED if ransac_seed is None else ransac_seed
             matches = registration.pairwise_rgldm(
                 points, models, model=refine, num_neighbors=num_neighbors, redundancy=redundancy,
-                ratio_of_distance=ratio_of_distance, difference_threshold=difference_threshold,
+                ratio_of_distance=3.0 if ratio_of_distance is None else ratio_of_distance,
+                difference_threshold=difference_threshold,
+                max_epsilon=max_epsilon, min_inlier_ratio=min_inlier_ratio, min_inlier_factor=min_inlier_factor,
+                num_iterations=num_iterations, seed=seed, device=device)
+        elif matching == "geometric_hashing":   # rotation invariant candidates, the same host RANSAC
+            from . import registration
+            seed = registration.RANSAC_SEED if ransac_seed is None else ransac_seed
+            matches = registration.pairwise_geometric_hashing(
+                points, models, model=refine,
+                ratio_of_distance=10.0 if ratio_of_distance is None else ratio_of_distance,
+                difference_threshold=difference_threshold,
                 max_epsilon=max_epsilon, min_inlier_ratio=min_inlier_ratio, min_inlier_factor=min_inlier_factor,
                 num_iterations=num_iterations, seed=seed, device=device)
         else:

@@ -18,6 +18,16 @@ csrc/rgldm.hip), bit-exact against the reference's arithmetic; there is no CPU p
 order of neighbours at exactly the same float distance is unpinned (lower index first here;
 the reference's fiji.util.KDTree is not in its tree).
 
+RGLDM is translation invariant only.  The reference's "fast 3d geometric hashing (rotation
+invariant)" (geometrichashing/GeometricHashingPairwise.java:45-86, GeometricHasher.java:54-116,
+mpicbg/pointdescriptor/LocalCoordinateSystemPointDescriptor.java) describes a point by its 3
+nearest neighbours in their own local coordinate system -- six floats -- and takes an A point as
+a candidate when its best B descriptor is below ``difference_threshold`` (50) and its distance
+times ``ratio_of_distance`` (10) not above the second best's.  ``gh_candidates`` /
+``gh_descriptors`` run that on the GPU (``spim_gh_match`` / ``spim_gh_descriptors``,
+csrc/geohash.hip), bit-exact too; unpinned is the ranking of B descriptors (by the float root
+of the distance, lower index first on equal floats, NaN not ranked).
+
 ``ransac`` restates ``RANSAC.computeRANSAC`` (spim/process/interestpointregistration/
 RANSAC.java:21-110) over mpicbg's ``Model.filterRansac`` on the host, in NumPy, with the
 model fits of ``globalopt.fit``.  Parity unpinned: mpicbg is not in the reference tree, so
@@ -46,7 +56,8 @@ import numpy as np
 from . import _lib, globalopt
 from ._lib import check
 
-__all__ = ["rgldm_candidates", "descriptors", "ransac", "pairwise_rgldm", "register", "tile_sizes"]
+__all__ = ["rgldm_candidates", "descriptors", "ransac", "pairwise_rgldm", "register", "tile_sizes",
+           "gh_candidates", "gh_descriptors", "gh_tile_sizes", "pairwise_geometric_hashing"]
 
 RANSAC_SEED = 4711
 
@@ -112,6 +123,56 @@ def rgldm_candidates(pa, pb, num_neighbors: int = 3, redundancy: int = 1, ratio_
     check(lib.spim_rgldm_match(aptr, na, bptr, nb, C.byref(p), C.c_void_p(idx.ctypes.data),
                                C.c_void_p(best.ctypes.data), C.c_void_p(second.ctypes.data),
                                C.c_void_p(ia.ctypes.data), C.c_void_p(ib.ctypes.data), na, C.byref(n)))
+    ia, ib = ia[:n.value].copy(), ib[:n.value].copy()
+    return (ia, ib, idx, best, second) if return_all else (ia, ib)
+
+
+def _gh_params(lib, ratio_of_distance, difference_threshold, device, b_split=0):
+    p = _lib.GhParams()
+    lib.spim_gh_params_default(C.byref(p))
+    p.ratio_of_distance, p.difference_threshold = float(ratio_of_distance), float(difference_threshold)
+    p.b_split, p.device = int(b_split), int(device)
+    return p
+
+
+def gh_tile_sizes():
+    """(A descriptors per block, B descriptors per LDS tile) of the geometric hashing
+    matching kernel."""
+    a, b = C.c_int32(0), C.c_int32(0)
+    _lib.load().spim_gh_tiles(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
+
+
+def gh_descriptors(points, device: int = 0):
+    """createLocalCoordinateSystemPointDescriptors (GeometricHasher.java:87-116) of at least
+    4 points: (neighbors (n, 3) int32 -- the nearest other points in ascending float distance
+    --, desc (n, 6) float32 -- ax bx by cx cy cz of LocalCoordinateSystemPointDescriptor)."""
+    lib = _lib.load()
+    p = _gh_params(lib, 10.0, 50.0, device)
+    ptr, n, _keep = _points(points)
+    nbr = np.empty((n, 3), np.int32)
+    desc = np.empty((n, 6), np.float32)
+    check(lib.spim_gh_descriptors(ptr, n, C.byref(p), C.c_void_p(nbr.ctypes.data), C.c_void_p(desc.ctypes.data)))
+    return nbr, desc
+
+
+def gh_candidates(pa, pb, ratio_of_distance: float = 10.0, difference_threshold: float = 50.0, device: int = 0,
+                  return_all: bool = False, b_split: int = 0):
+    """GeometricHasher.extractCorrespondenceCandidates (rotation invariant) over two (n, 3)
+    point lists (numpy arrays or CUDA torch tensors, x, y, z): (ia, ib), candidate k pairs
+    pa[ia[k]] with pb[ib[k]], in ascending ia; with ``return_all`` also best_idx, best and
+    second over every point of pa.  Fewer than 4 points in either list: no candidates.
+    ``b_split`` forces the partitions of B (0 = auto; the result does not depend on it)."""
+    lib = _lib.load()
+    p = _gh_params(lib, ratio_of_distance, difference_threshold, device, b_split)
+    aptr, na, _ka = _points(pa)
+    bptr, nb, _kb = _points(pb)
+    idx, best, second = np.empty(na, np.int32), np.empty(na, np.float64), np.empty(na, np.float64)
+    ia, ib = np.empty(max(na, 1), np.int32), np.empty(max(na, 1), np.int32)   # at most one candidate per A point
+    n = C.c_int64(0)
+    check(lib.spim_gh_match(aptr, na, bptr, nb, C.byref(p), C.c_void_p(idx.ctypes.data),
+                            C.c_void_p(best.ctypes.data), C.c_void_p(second.ctypes.data),
+                            C.c_void_p(ia.ctypes.data), C.c_void_p(ib.ctypes.data), na, C.byref(n)))
     ia, ib = ia[:n.value].copy(), ib[:n.value].copy()
     return (ia, ib, idx, best, second) if return_all else (ia, ib)
 
@@ -209,13 +270,45 @@ def pairwise_rgldm(points, models, pairs=None, model: str = "affine", num_neighb
     return out
 
 
-def register(points, models, model: str = "affine", fixed=(0,), **kw):
+def pairwise_geometric_hashing(points, models, pairs=None, model: str = "affine", ratio_of_distance: float = 10.0,
+                               difference_threshold: float = 50.0, max_epsilon: float = 5.0,
+                               min_inlier_ratio: float = 0.1, min_inlier_factor: float = 3.0,
+                               num_iterations: int = 1000, seed: int = RANSAC_SEED, device: int = 0,
+                               candidates=None):
+    """GeometricHashingPairwise.call (:45-86) over all view pairs (or ``pairs``): as
+    ``pairwise_rgldm`` with the rotation invariant geometric hashing candidates
+    (``gh_candidates``) in place of RGLDM's, so the ``models`` need not be rotationally
+    right.  ``candidates``: a callable (pa, pb, ratio_of_distance=, difference_threshold=)
+    -> (ia, ib) to use in place of the GPU matcher."""
+    world = [globalopt.apply(np.asarray(m, np.float64).reshape(3, 4), np.asarray(p, np.float64).reshape(-1, 3))
+             for p, m in zip(points, models)]
+    if pairs is None:
+        pairs = [(a, b) for a in range(len(world)) for b in range(a + 1, len(world))]
+    kw = dict(ratio_of_distance=ratio_of_distance, difference_threshold=difference_threshold)
+    out = []
+    for a, b in pairs:
+        if candidates is None:
+            ia, ib = gh_candidates(world[a], world[b], device=device, **kw)
+        else:
+            ia, ib = candidates(world[a], world[b], **kw)
+        ca, cb = world[a][ia], world[b][ib]
+        inl, _, _ = ransac(ca, cb, model, max_epsilon, min_inlier_ratio, min_inlier_factor, num_iterations, seed)
+        if len(inl):
+            out.append(globalopt.PairwiseMatch(a, b, ca[inl], cb[inl]))
+    return out
+
+
+def register(points, models, model: str = "affine", fixed=(0,), matching: str = "rgldm", **kw):
     """Descriptor-based registration of the views from their detections and approximate
-    models: ``pairwise_rgldm`` (its keywords pass through), ``globalopt.compute`` and
+    models: ``pairwise_rgldm`` -- or, with ``matching`` = "geometric_hashing",
+    ``pairwise_geometric_hashing`` -- (its keywords pass through), ``globalopt.compute`` and
     ``globalopt.concatenate``.  Returns (the refined 3x4 models, the GlobalOptResult -- None
     when no pair has inliers, the models then are the given ones)."""
+    if matching not in ("rgldm", "geometric_hashing"):
+        raise ValueError(f"matching must be 'rgldm' or 'geometric_hashing', not {matching!r}")
     models = [np.asarray(m, np.float64).reshape(3, 4) for m in models]
-    matches = pairwise_rgldm(points, models, model=model, **kw)
+    pairwise = pairwise_rgldm if matching == "rgldm" else pairwise_geometric_hashing
+    matches = pairwise(points, models, model=model, **kw)
     res = globalopt.compute(len(models), matches, model=model, fixed=fixed)
     if res is not None:
         models = [globalopt.concatenate(c, m) for c, m in zip(res.models, models)]
