@@ -502,6 +502,47 @@ int spim_gh_match(const double* a, int64_t na, const double* b, int64_t nb,
                   int32_t* cand_a, int32_t* cand_b, int64_t cap, int64_t* count);
 
 /* ======================================================================
+ * 6e. Pairwise registration, "Iterative closest-point (ICP, no invariance)": one iteration's
+ *     correspondence search -- mpicbg/icp/ICP.java:91-115 (apply, assign), :208-317
+ *     (removeAmbigousMatches), SimplePointMatchIdentification.java:32-48,
+ *     spim/process/interestpointregistration/Detection.java:96-115 (distanceTo, get).  The
+ *     target list is moved by the current model (absolute, target coordinates -> reference
+ *     frame), the reference list never; the loop and the model fits of
+ *     IterativeClosestPointPairwise.java:40-122 stay with the caller.  Points as in 6c.
+ *     Bit-exact against the reference's arithmetic; among equal float distances the lower
+ *     target index is the nearest (the reference's kd-tree is not in its tree).
+ * ====================================================================== */
+typedef struct spim_icp_params {
+    float   max_distance;    /* 5   (float in the reference, widened to double at use) */
+    int32_t max_iterations;  /* 100 (the caller's loop; spim_icp_assign does not read it) */
+    int32_t t_split;         /* 0 = auto; >0 forces that many partitions of the target (tests) */
+    int32_t device;
+} spim_icp_params;
+
+void spim_icp_params_default(spim_icp_params* p);
+
+/* The assignment kernel's tile sizes: reference points per block, target points per LDS tile.
+ * Host only: needs no GPU. */
+void spim_icp_tiles(int32_t* ref_block, int32_t* target_tile);
+
+/* One ICP iteration up to the fit.  Every target point becomes w = model * l in double, each
+ * row ((m0 x + m1 y) + m2 z) + m3 with every product and sum rounded on its own (model: 12
+ * doubles, row-major 3x4, host or device; NULL = the identity).  For every reference point
+ * nearest[r] = the target with the smallest Detection.distanceTo (float coordinates, float
+ * differences, a double sum, (float) Math.sqrt; lowest index among equal floats) and dist[r]
+ * that float; nt == 0: -1 and FLT_MAX.  (nearest[r], r) is a match when (double) dist[r] <=
+ * (double) max_distance; matches whose target another match names too are removed
+ * (*ambiguous = how many) and the others written in ascending r: match_t[k], match_r[k].
+ * *count = their number; more than cap is SPIMDECON_ERR_ARG with *count still the needed size
+ * (nearest / dist are written all the same).  nt == 0 or nr == 0: no matches, status OK.
+ * Coordinates not finite (as double or as float, before or after the model) or a list longer
+ * than 2^31 - 1: SPIMDECON_ERR_ARG.  The result does not depend on t_split. */
+int spim_icp_assign(const double* target, int64_t nt, const double* reference, int64_t nr,
+                    const double* model, const spim_icp_params* p, int32_t* nearest, float* dist,
+                    int32_t* match_t, int32_t* match_r, int64_t cap, int64_t* count,
+                    int64_t* ambiguous);
+
+/* ======================================================================
  * 7. Deconvolution input preparation --
  *    spim/process/fusion/deconvolution/ProcessForDeconvolution.java:159-384:
  *    each view resampled into the fused bounding box through the inverse of

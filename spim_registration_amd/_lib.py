@@ -95,6 +95,15 @@ class GhParams(C.Structure):
     ]
 
 
+class IcpParams(C.Structure):
+    _fields_ = [
+        ("max_distance", C.c_float),
+        ("max_iterations", C.c_int32),
+        ("t_split", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class Peak(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32),
                 ("intensity", C.c_float), ("is_min", C.c_int32), ("is_max", C.c_int32)]
@@ -194,6 +203,10 @@ SIGNATURES = {
     "spim_gh_descriptors": (C.c_int, [C.c_void_p, _i64, C.POINTER(GhParams), C.c_void_p, C.c_void_p]),
     "spim_gh_match": (C.c_int, [C.c_void_p, _i64, C.c_void_p, _i64, C.POINTER(GhParams), C.c_void_p,
                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _i64, _pi64]),
+    "spim_icp_params_default": (None, [C.POINTER(IcpParams)]),
+    "spim_icp_tiles": (None, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "spim_icp_assign": (C.c_int, [C.c_void_p, _i64, C.c_void_p, _i64, C.c_void_p, C.POINTER(IcpParams), C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, _i64, _pi64, _pi64]),
     "spim_psf_release_workspace": (C.c_int, [C.c_int]),
     "spim_save_interest_points": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(InterestPointC),
                                             C.POINTER(C.c_int32), C.c_int64]),

@@ -116,7 +116,8 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
                       redundancy: int = 1, ratio_of_distance: float | None = None,
                       difference_threshold: float = 50.0, max_epsilon: float = 5.0,
                       min_inlier_ratio: float = 0.1, min_inlier_factor: float = 3.0,
-                      num_iterations: int = 1000, ransac_seed: int | None = None) -> TimepointResult:
+                      num_iterations: int = 1000, ransac_seed: int | None = None, icp: bool = False,
+                      icp_max_distance: float = 5.0, icp_max_iterations: int = 100) -> TimepointResult:
     """views: per view a [z, y, x] float32 torch tensor on the GPU (the acquired
     stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z);
     dog_extension: the detect stage's 'mirror' (accurate) or 'border' (approximate) GPU
@@ -128,8 +129,13 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
     parameters of ``registration.pairwise_rgldm``, or 'geometric_hashing' (rotation
     invariant: ratio_of_distance, difference_threshold and the RANSAC parameters of
     ``registration.pairwise_geometric_hashing``); ratio_of_distance None = the matcher's
-    default, 3 for RGLDM and 10 for geometric hashing."""
+    default, 3 for RGLDM and 10 for geometric hashing; icp (needs ``refine``): after that
+    matching's global optimisation, ``registration.register_icp`` with model ``refine``,
+    icp_max_distance and icp_max_iterations on the models it produced -- the reference's ICP
+    run after a descriptor-based one; ``globalopt`` of the result then is the ICP run's."""
     import torch
+    if icp and refine is None:
+        raise ValueError("icp=True needs refine (the model of the ICP registration)")
     if detector not in ("dog", "dom"):
         raise ValueError(f"detector must be 'dog' or 'dom', not {detector!r}")
     if matching not in ("nearest", "rgldm", "geometric_hashing"):
@@ -184,6 +190,13 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
             if gres.failure and log:
                 log(gres.failure)
             models = [globalopt.concatenate(c, m) for c, m in zip(gres.models, models)]
+        if icp:   # every detection re-matched under the models so far (assignment on the views' device)
+            from . import registration
+            models, gres = registration.register_icp(points, models, model=refine, fixed=(0,),
+                                                     max_distance=icp_max_distance,
+                                                     max_iterations=icp_max_iterations, device=device)
+            if gres is not None and gres.failure and log:
+                log(gres.failure)
         t = lap("register", t)
     corr = corresponding_detections(points, models, radius, device=f"cuda:{device}")   # 2. (registration given)
     t = lap("correspondences", t)

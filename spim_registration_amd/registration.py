@@ -46,6 +46,17 @@ model fits of ``globalopt.fit``.  Parity unpinned: mpicbg is not in the referenc
 given seed.  Regularised models (``InterpolatedAffineModel3D``) are out of scope: ``model``
 is "translation", "rigid" or "affine".  RANSAC stays on the host on purpose: 10^3
 hypotheses over a few thousand candidates take milliseconds.
+
+The reference's third matcher, "Iterative closest-point (ICP, no invariance)"
+(icp/IterativeClosestPointPairwise.java:40-122, mpicbg/icp/ICP.java:91-115 and :208-317,
+SimplePointMatchIdentification.java:32-48), is a registration run of its own after a descriptor
+one: it re-matches every detection under the current model, which multiplies the
+correspondences.  ``icp_assign`` runs one iteration's search on the GPU (``spim_icp_assign``,
+csrc/icp.hip: the model applied to the target list, per reference point the nearest target by
+``Detection.distanceTo``, the threshold, ambiguous matches removed), bit-exact; ``icp`` is the
+loop with the fits of ``globalopt.fit``, ``pairwise_icp`` / ``register_icp`` the entry points.
+Unpinned: the order among equal float distances (lower target index first; the reference's
+kd-tree is not in its tree) and mpicbg's ``fit`` / ``apply`` (restated in ``globalopt``).
 """
 from __future__ import annotations
 
@@ -57,7 +68,8 @@ from . import _lib, globalopt
 from ._lib import check
 
 __all__ = ["rgldm_candidates", "descriptors", "ransac", "pairwise_rgldm", "register", "tile_sizes",
-           "gh_candidates", "gh_descriptors", "gh_tile_sizes", "pairwise_geometric_hashing"]
+           "gh_candidates", "gh_descriptors", "gh_tile_sizes", "pairwise_geometric_hashing",
+           "icp_tile_sizes", "icp_assign", "icp", "pairwise_icp", "register_icp"]
 
 RANSAC_SEED = 4711
 
@@ -175,6 +187,121 @@ def gh_candidates(pa, pb, ratio_of_distance: float = 10.0, difference_threshold:
                             C.c_void_p(ia.ctypes.data), C.c_void_p(ib.ctypes.data), na, C.byref(n)))
     ia, ib = ia[:n.value].copy(), ib[:n.value].copy()
     return (ia, ib, idx, best, second) if return_all else (ia, ib)
+
+
+def icp_tile_sizes():
+    """(reference points per block, target points per LDS tile) of the ICP assignment kernel."""
+    a, b = C.c_int32(0), C.c_int32(0)
+    _lib.load().spim_icp_tiles(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
+
+
+def icp_assign(target, reference, model=None, max_distance: float = 5.0, device: int = 0, return_all: bool = False,
+               t_split: int = 0):
+    """One ICP iteration up to the fit (ICP.runICPIteration, ICP.java:91-101) over two (n, 3)
+    point lists (numpy arrays or CUDA torch tensors): the target moved by the 3x4 ``model``
+    (None = the identity), per reference point its nearest target by ``Detection.distanceTo``
+    (lower index among equal floats), a match when that float distance is <=
+    ``(float) max_distance``, and the matches that share a target removed.  Returns (it, ir),
+    match k pairs target[it[k]] with reference[ir[k]], in ascending ir; with ``return_all`` also
+    nearest (int32) and dist (float32) over every reference point and the number of ambiguous
+    matches removed.  ``t_split`` forces the partitions of the target (0 = auto; the result
+    does not depend on it)."""
+    lib = _lib.load()
+    p = _lib.IcpParams()
+    lib.spim_icp_params_default(C.byref(p))
+    p.max_distance, p.t_split, p.device = float(max_distance), int(t_split), int(device)
+    tptr, nt, _kt = _points(target)
+    rptr, nr, _kr = _points(reference)
+    m = None if model is None else np.ascontiguousarray(np.asarray(model, np.float64).reshape(12))
+    nearest, dist = np.empty(nr, np.int32), np.empty(nr, np.float32)
+    it, ir = np.empty(max(nr, 1), np.int32), np.empty(max(nr, 1), np.int32)   # at most one match per reference point
+    n, amb = C.c_int64(0), C.c_int64(0)
+    check(lib.spim_icp_assign(tptr, nt, rptr, nr, None if m is None else C.c_void_p(m.ctypes.data), C.byref(p),
+                              C.c_void_p(nearest.ctypes.data), C.c_void_p(dist.ctypes.data),
+                              C.c_void_p(it.ctypes.data), C.c_void_p(ir.ctypes.data), nr, C.byref(n), C.byref(amb)))
+    it, ir = it[:n.value].copy(), ir[:n.value].copy()
+    return (it, ir, nearest, dist, int(amb.value)) if return_all else (it, ir)
+
+
+def icp(pa, pb, model: str = "affine", max_distance: float = 5.0, max_iterations: int = 100, device: int = 0,
+        assign=None):
+    """IterativeClosestPointPairwise.call (:40-122) over the target list ``pa`` and the reference
+    list ``pb`` ((n, 3), one common frame): from the identity, assign (``icp_assign`` on GPU
+    ``device``) under the current model, fit ``model`` to the matches (``globalopt.fit``, pa ->
+    pb; the model is absolute, not incremental), until an iteration's number of matches and mean
+    error both equal the previous one's, ``max_iterations`` at the most.  Returns (it, ir, the
+    3x4 model, the mean error of the matches under it, the reference's iteration count ``i``);
+    fewer points than the model's minimum in a list, or a fit that fails
+    (NotEnoughDataPoints, IllDefinedDataPoints): ((0,) indices twice, None, NaN, i).  The lists
+    are uploaded once; the errors are NumPy's on the host.  ``assign``: a callable with
+    ``icp_assign``'s signature to use in place of the GPU (the tests feed the restatement
+    through the same loop)."""
+    if model not in globalopt.MIN_MATCHES:
+        raise ValueError(f"model must be one of {sorted(globalopt.MIN_MATCHES)}")
+    pa = np.ascontiguousarray(np.asarray(pa, np.float64).reshape(-1, 3))
+    pb = np.ascontiguousarray(np.asarray(pb, np.float64).reshape(-1, 3))
+    empty = np.zeros(0, np.int32)
+    least = globalopt.MIN_MATCHES[model]
+    if len(pa) < least or len(pb) < least:   # "Not enough detections to match"
+        return empty, empty, None, float("nan"), 0
+    if assign is None:
+        import torch
+        ta, tb = (torch.tensor(x, dtype=torch.float64, device=f"cuda:{int(device)}") for x in (pa, pb))
+        kw = dict(max_distance=max_distance, device=device)
+        assign = icp_assign
+    else:
+        ta, tb = pa, pb
+        kw = dict(max_distance=max_distance)
+    m = np.hstack([np.eye(3), np.zeros((3, 1))])
+    i, last_n, last_err = 0, 0, 0.0
+    while True:
+        it, ir = assign(ta, tb, model=m, **kw)
+        try:
+            m = globalopt.fit(model, pa[it], pb[ir], np.ones(len(it)))
+        except (globalopt.NotEnoughDataPoints, globalopt.IllDefinedDataPoints):
+            return empty, empty, None, float("nan"), i
+        err = float(np.linalg.norm(globalopt.apply(m, pa[it]) - pb[ir], axis=1).mean())   # PointMatch.meanDistance
+        converged = last_n == len(it) and last_err == err
+        last_n, last_err = len(it), err
+        if converged:
+            break
+        i += 1
+        if not i < int(max_iterations):
+            break
+    return it, ir, m, err, i
+
+
+def pairwise_icp(points, models, pairs=None, model: str = "affine", max_distance: float = 5.0,
+                 max_iterations: int = 100, device: int = 0, assign=None):
+    """IterativeClosestPointPairwise.call over all view pairs (or ``pairs``, (a, b) tuples): the
+    views' detections mapped by their current ``models``, view a the target and view b the
+    reference of ``icp``.  Returns the pairs with matches as ``globalopt.PairwiseMatch`` over
+    world points under ``models`` (the last iteration's matches are candidates and inliers
+    alike; the pair's model is not passed on, the global optimisation refits)."""
+    world = [globalopt.apply(np.asarray(m, np.float64).reshape(3, 4), np.asarray(p, np.float64).reshape(-1, 3))
+             for p, m in zip(points, models)]
+    if pairs is None:
+        pairs = [(a, b) for a in range(len(world)) for b in range(a + 1, len(world))]
+    out = []
+    for a, b in pairs:
+        it, ir, _, _, _ = icp(world[a], world[b], model, max_distance, max_iterations, device, assign)
+        if len(it):
+            out.append(globalopt.PairwiseMatch(a, b, world[a][it], world[b][ir]))
+    return out
+
+
+def register_icp(points, models, model: str = "affine", fixed=(0,), **kw):
+    """ICP registration of the views from their detections and models that are already close
+    (the reference runs it after a descriptor-based registration): ``pairwise_icp`` (its
+    keywords pass through), ``globalopt.compute`` and ``globalopt.concatenate``.  Returns what
+    ``register`` returns."""
+    models = [np.asarray(m, np.float64).reshape(3, 4) for m in models]
+    matches = pairwise_icp(points, models, model=model, **kw)
+    res = globalopt.compute(len(models), matches, model=model, fixed=fixed)
+    if res is not None:
+        models = [globalopt.concatenate(c, m) for c, m in zip(res.models, models)]
+    return models, res
 
 
 def _inliers(kind, pa, pb, sel, eps):
