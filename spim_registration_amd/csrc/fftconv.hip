@@ -229,6 +229,8 @@ struct XArgs {
     uint32_t nvox;
     // packed row pairs processed by this launch: [pb0, pb0 + pn0) then [pb1, pb1 + pn1)
     int pb0, pn0, pb1, pn1;
+    int pn_full;  // > 0: the launch is the prefix [0, pn0) of a pass over pn_full pairs (PairRanges::full)
+    int pofs;     // first stats partial of the launch's blocks (k_xtile)
 };
 
 // linear index of a launch -> packed row pair (-1 past the ranges)
@@ -534,6 +536,15 @@ unsigned launch_xtile(const XArgs& a, Store st, const SpectralPlan& p, hipStream
     const size_t lds = xt_lds(L, NP, xt_twg(L, NP));
     if (lds > 160 * 1024) return 0;
     const unsigned grid = unsigned(std::max<int64_t>(1, ceil_div(int64_t(a.pn0) + a.pn1, int64_t(NP))));
+    // a prefix of a longer pass: tile t holds the pairs it holds there, and its block writes
+    // the partial that pass's block would (the tiles left out add zeros to the statistics)
+    unsigned nparts = grid;
+    if (a.pn_full > 0) {
+        SD_CHECK(a.pb0 == 0 && a.pn1 == 0 && a.pn0 > 0 && a.pn0 <= a.pn_full, SPIMDECON_ERR_STATE,
+                 "a prefix launch must start at pair 0");
+        nparts = unsigned(ceil_div(int64_t(a.pn_full), int64_t(NP)));
+        b.pofs = SD_XT_REV ? int(nparts - grid) : 0;
+    }
     const int sv = st == Store::F32 ? 0 : 1;
     bool done = false;
     const bool tik = MODE == XM_UPDATE && a.lambda > 0.0;
@@ -567,7 +578,7 @@ unsigned launch_xtile(const XArgs& a, Store st, const SpectralPlan& p, hipStream
         SD_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_xt_stamp), h, sizeof(h)));
     }
 #endif
-    return grid;
+    return nparts;
 }
 
 // k_xrows when the rows allow 16-B voxel access; returns the grid, 0 = use k_xpass
@@ -611,6 +622,8 @@ unsigned launch_x(const XArgs& a, Store st, const SpectralPlan& p, hipStream_t s
             return gt;
         }
     }
+    // (the row kernels stride their grid over the pairs: another partials layout)
+    SD_CHECK(a.pn_full == 0, SPIMDECON_ERR_STATE, "a prefix update launch needs the x tiles");
     if constexpr (MODE == XM_QUOT || MODE == XM_UPDATE) {
         if (const unsigned gr = launch_xrows<MODE>(a, st, p, s)) {
             if (MODE == XM_UPDATE) p.xmode_update = 1;
@@ -796,6 +809,8 @@ EngineKnobs EngineKnobs::from_env() {
     k.ypf = !off("SPIMDECON_YPF");
     k.zkd = !off("SPIMDECON_ZKD");
     k.zdirect = zdirect_env();
+    k.ext_c2 = !off("SPIMDECON_EXT_C2");
+    k.ext_c1 = !off("SPIMDECON_EXT_C1");
     return k;
 }
 
@@ -849,8 +864,15 @@ void SpectralPlan::create(const SlabGeom& geom, bool allow_2f, bool z_fft, const
     SD_HIP(hipMemcpy(row_one.p, ro.data(), nrows * sizeof(int), hipMemcpyHostToDevice));
 }
 
-void engine_forward_psi(const SpectralPlan& p, const float* psi, float2* C, hipStream_t s) {
+void engine_forward_psi(const SpectralPlan& p, const float* psi, float2* C, hipStream_t s,
+                        const PairRanges* pr) {
     XArgs a = base_args(p);
+    if (pr) {
+        a.pb0 = pr->b0;
+        a.pn0 = pr->n0;
+        a.pb1 = pr->b1;
+        a.pn1 = pr->n1;
+    }
     a.psi_in = psi;
     a.Cout = C;
     launch_x<XM_PSI>(a, Store::F32, p, s);
@@ -974,7 +996,39 @@ int engine_zpass_mode(const SpectralPlan& p, bool compact) {
     return engine_zdirect_ok(p) ? 3 : 1;
 }
 
-void engine_zpass_compact(const SpectralPlan& p, float2* C, const float2* Kc, hipStream_t s) {
+bool engine_ext_planes_ok(const SpectralPlan& p) {
+    const SlabGeom& g = p.g;
+    // the x tiles take this slab (launch_xtile and x_buffer_args; the session's buffers are
+    // device allocations, aligned)
+    const int L = int(g.Mx);
+    bool xt = false;
+#define SD_XT_HAS(A, B) xt = xt || L == (A) * (B);
+    SD_X2F_SIZES(SD_XT_HAS)
+#undef SD_XT_HAS
+    for (int mode : {int(XM_PSI), int(XM_QUOT), int(XM_UPDATE)})
+        xt = xt && xt_lds(L, xt_np(mode, L), xt_twg(L, xt_np(mode, L))) <= 160 * 1024;
+    xt = xt && uint64_t(p.spectrum_elems()) * sizeof(float2) < kOOB && uint64_t(g.nx) * g.ny * g.nz * 4 < kOOB;
+    return xt && engine_zdirect_ok(p) && p.fx.n1 != 0 && p.fy.n1 != 0 && g.nx % 4 == 0 && g.My % 2 == 0 && g.cz >= 1 &&
+           g.Mz == g.nz + 2 * g.cz && g.z0 == 0 && g.nzg == g.nz && g.nz >= g.cz + 1;
+}
+
+// Mirrored loads read interior planes, which the pass overwrites chunk by chunk.  Chunk c
+// loads before it computes and while chunk c - 1 stores, so a plane it needs must lie at or
+// past its own first output.  Upper extension planes mirror [nz - 1 - cz, nz - 2]: inside the
+// last chunk when that holds cz + 1 planes.  Lower ones mirror [1, cz] and carry non-zero
+// taps for the outputs below cz only: chunk 0 when H >= cz.  (Past the taps a window reads
+// either side of such a plane, times zero, as it already does where it wraps.)
+bool engine_zmirror_ok(const SpectralPlan& p) {
+    if (!engine_ext_planes_ok(p)) return false;
+    const ZChunk zc = zdmc_plan(p.g.nz, zdirect_kc_bound(p.g.cz));
+    if (zc.H <= 0) return false;
+    const int64_t nch = ceil_div(p.g.nz, int64_t(zc.H));
+    const int64_t last = p.g.nz - (nch - 1) * zc.H;
+    return nch == 1 || (zc.H >= p.g.cz && last >= p.g.cz + 1);
+}
+
+void engine_zpass_compact(const SpectralPlan& p, float2* C, const float2* Kc, hipStream_t s, bool zmirror) {
+    SD_CHECK(!zmirror || engine_zmirror_ok(p), SPIMDECON_ERR_STATE, "mirrored z planes not available");
     if (!engine_zdirect_ok(p)) {
         const bool ok = launch_col2f<2, 5>(p, p.fz, C, Kc, s, 0, -1, p.g.cz, int(p.g.nz));
         SD_CHECK(ok, SPIMDECON_ERR_ARG, "compact-kernel z pass not available");
@@ -1006,7 +1060,7 @@ void engine_zpass_compact(const SpectralPlan& p, float2* C, const float2* Kc, hi
         }();                                                                                                  \
         const unsigned grid = unsigned(std::min<int64_t>(ntiles, 256 * per_cu));                              \
         hipLaunchKernelGGL((k_zdmc<KCV, OPTV, KDV>), dim3(grid), dim3(kZdThreads), lds, s, p.g, nflat, C, Kc,  \
-                           p.g.cz, zc.H, bytes, kscale);                                                      \
+                           p.g.cz, zc.H, bytes, kscale, int(zmirror));                                                    \
         done = true;                                                                                          \
     }
 #define SD_ZC3(KCV) SD_ZC(KCV, 16, 0) SD_ZC(KCV, 12, 0) SD_ZC(KCV, 8, 0)
@@ -1019,10 +1073,16 @@ void engine_zpass_compact(const SpectralPlan& p, float2* C, const float2* Kc, hi
     SD_HIP(hipGetLastError());
 }
 
-void engine_ypass(const SpectralPlan& p, float2* C, bool inv, hipStream_t s) {
+void engine_ypass(const SpectralPlan& p, float2* C, bool inv, hipStream_t s, int fwd_planes) {
     // the inverse feeds the x passes, which read the nz interior planes only
-    if (inv) launch_col<1, true, 0>(p, p.fy, C, nullptr, s, int(p.g.nz));
-    else launch_col<1, false, 0>(p, p.fy, C, nullptr, s);
+    if (inv) {
+        launch_col<1, true, 0>(p, p.fy, C, nullptr, s, int(p.g.nz));
+    } else if (fwd_planes >= 0) {
+        SD_CHECK(engine_ypass_planes(p, C, 0, fwd_planes, s), SPIMDECON_ERR_STATE,
+                 "y pass of a plane range not available");
+    } else {
+        launch_col<1, false, 0>(p, p.fy, C, nullptr, s);
+    }
 }
 
 bool engine_ypass_planes2(const SpectralPlan& p, float2* C, int z0, int z1, int z2, int z3, hipStream_t s) {
@@ -1055,6 +1115,13 @@ PairRanges all_pairs(const SpectralPlan& p) {
     return r;
 }
 
+PairRanges interior_pairs(const SpectralPlan& p) {
+    SD_CHECK(p.g.My % 2 == 0, SPIMDECON_ERR_STATE, "row pairs straddle the z planes");
+    PairRanges r;
+    r.n0 = int(p.g.My * p.g.nz / 2);
+    return r;
+}
+
 void engine_quotient(const SpectralPlan& p, Store st, const float2* Cin, const void* img,
                      float2* Cout, const PairRanges& pr, hipStream_t s) {
     XArgs a = base_args(p);
@@ -1076,6 +1143,7 @@ int64_t engine_update(const SpectralPlan& p, Store st, const float2* Cin, const 
     a.pn0 = pr.n0;
     a.pb1 = pr.b1;
     a.pn1 = pr.n1;
+    a.pn_full = pr.full;
     a.Cin = Cin;
     a.Cout = Cout;
     a.psi_in = psi_in;

@@ -44,8 +44,10 @@ struct Fft1D {
 //   SPIMDECON_YPF=0      y passes at one block per CU without the register prefetch
 //   SPIMDECON_ZKD=0      no compile-time trim of the zero outer taps in the direct z pass
 //   SPIMDECON_ZDIRECT=0  the fused FFT z pass (k_col2f MODE 5) instead of the direct one
+//   SPIMDECON_EXT_C2=0   the quotient side computes its constant extension planes every view
+//   SPIMDECON_EXT_C1=0   the update side computes and stores its mirror extension planes
 struct EngineKnobs {
-    bool ypf = true, zkd = true, zdirect = true;
+    bool ypf = true, zkd = true, zdirect = true, ext_c2 = true, ext_c1 = true;
     static EngineKnobs from_env();
 };
 
@@ -81,8 +83,27 @@ int64_t engine_fast_size(int64_t need, bool even, int policy = 0);
 bool engine_slab_fits(int64_t nx, int64_t ny, int64_t nzs, const int halo[3], int policy);
 
 // ---- passes (all asynchronous on `s`) ----
-// psi -> C (x-spectra of the mirror-extended psi rows)
-void engine_forward_psi(const SpectralPlan& p, const float* psi, float2* C, hipStream_t s);
+// packed row pairs (rows 2i, 2i+1 of the My*Mz padded rows) an x pass covers:
+// [b0, b0 + n0) then [b1, b1 + n1).  full > 0: the launch is the prefix [0, n0) of a pass
+// over `full` pairs whose other pairs change no statistic; an update pass then keeps the
+// partials layout (and count) of the full pass, the left-out entries being zero already.
+struct PairRanges {
+    int b0 = 0, n0 = 0, b1 = 0, n1 = 0, full = 0;
+};
+// all packed row pairs of a slab
+PairRanges all_pairs(const SpectralPlan& p);
+// the pairs of the nz interior planes (My even)
+PairRanges interior_pairs(const SpectralPlan& p);
+// A slab without neighbours whose z-extension planes [nz, Mz) need not be computed: the
+// x tiles, the plane-range y pass and the direct z pass apply, rows pair up inside planes
+bool engine_ext_planes_ok(const SpectralPlan& p);
+// ... and the direct z pass may read the mirror of an extension plane in its place (no
+// chunk reads a plane an earlier chunk of its tile has overwritten)
+bool engine_zmirror_ok(const SpectralPlan& p);
+
+// psi -> C (x-spectra of the mirror-extended psi rows; of the pairs pr when given)
+void engine_forward_psi(const SpectralPlan& p, const float* psi, float2* C, hipStream_t s,
+                        const PairRanges* pr = nullptr);
 // small kernel (kx,ky,kz) -> full 3D spectrum in Kspec (scaled), uses `work` as scratch-free in place
 void engine_kernel_spectrum(const SpectralPlan& p, const float* d_kernel, int kx, int ky, int kz,
                             float scale, float2* Kspec, hipStream_t s);
@@ -102,9 +123,13 @@ int engine_zpass_mode(const SpectralPlan& p, bool compact);
 int64_t engine_kernel_compact_elems(const SpectralPlan& p);
 void engine_kernel_compact(const SpectralPlan& p, const float* d_kernel, int kx, int ky, int kz, float scale,
                            float2* work, float2* Kc, hipStream_t s);
-void engine_zpass_compact(const SpectralPlan& p, float2* C, const float2* Kc, hipStream_t s);
-// Y pass: in-place complex FFT along y (inverse when inv)
-void engine_ypass(const SpectralPlan& p, float2* C, bool inv, hipStream_t s);
+// zmirror (engine_zmirror_ok): the extension planes [nz, Mz) of C are not read; the planes
+// they mirror are (bit for bit the same spectra)
+void engine_zpass_compact(const SpectralPlan& p, float2* C, const float2* Kc, hipStream_t s,
+                          bool zmirror = false);
+// Y pass: in-place complex FFT along y (inverse when inv); a forward pass over the first
+// fwd_planes z planes only when fwd_planes >= 0
+void engine_ypass(const SpectralPlan& p, float2* C, bool inv, hipStream_t s, int fwd_planes = -1);
 // Forward y pass of the z planes [z0, z1) only (false: not available for this plan,
 // run engine_ypass instead)
 bool engine_ypass_planes(const SpectralPlan& p, float2* C, int z0, int z1, hipStream_t s);
@@ -112,14 +137,6 @@ bool engine_ypass_planes(const SpectralPlan& p, float2* C, int z0, int z1, hipSt
 bool engine_ypass_planes2(const SpectralPlan& p, float2* C, int z0, int z1, int z2, int z3, hipStream_t s);
 // Z pass: forward z FFT, multiply by K (when K != nullptr) and inverse z FFT
 void engine_zpass(const SpectralPlan& p, float2* C, const float2* K, hipStream_t s);
-// packed row pairs (rows 2i, 2i+1 of the My*Mz padded rows) an x pass covers:
-// [b0, b0 + n0) then [b1, b1 + n1)
-struct PairRanges {
-    int b0 = 0, n0 = 0, b1 = 0, n1 = 0;
-};
-// all packed row pairs of a slab
-PairRanges all_pairs(const SpectralPlan& p);
-
 // X pass A: conv1 result (Cin) -> quotient with img -> forward spectrum into Cout
 void engine_quotient(const SpectralPlan& p, Store st, const float2* Cin, const void* img,
                      float2* Cout, const PairRanges& pr, hipStream_t s);

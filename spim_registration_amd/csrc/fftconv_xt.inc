@@ -638,8 +638,8 @@ void k_xtile(XArgs a) {
                 ssum += sh_sum[i];
                 smax = fmaxf(smax, sh_max[i]);
             }
-            a.partials[2 * blockIdx.x] = ssum;
-            a.partials[2 * blockIdx.x + 1] = (double)smax;
+            a.partials[2 * (a.pofs + blockIdx.x)] = ssum;
+            a.partials[2 * (a.pofs + blockIdx.x) + 1] = (double)smax;
         }
     }
 }

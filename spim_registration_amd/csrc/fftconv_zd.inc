@@ -83,7 +83,7 @@ __host__ __device__ constexpr int zdc_lds(int KC, int OPT, int TX) {
 // runtime kc masks the taps as before.
 template <int KC, int OPT, int KD = 0>
 __global__ __launch_bounds__(kZdThreads) void k_zdmc(SlabGeom g, int64_t nflat, float2* C, const float2* Kc, int kc,
-                                                     int H, uint32_t bytes, float kscale) {
+                                                     int H, uint32_t bytes, float kscale, int zmir) {
     constexpr int TX = 32, NB = 2, NT = kZdThreads;
     constexpr int NQ = 2 * KC + 1;
     constexpr int W = OPT + 2 * KC - 2 * KD;   // window inputs per thread (from slot zb + KD)
@@ -138,6 +138,9 @@ __global__ __launch_bounds__(kZdThreads) void k_zdmc(SlabGeom g, int64_t nflat, 
                 int z = zc - KC + s;
                 z += z < 0 ? Mz : 0;
                 z %= Mz;
+                // zmir (Mz = nz + 2 kc, no neighbours): an extension plane is not in memory;
+                // the plane it mirrors, in [0, nz), holds the same spectra
+                if (zmir && z >= nz) z = z < nz + kc ? 2 * (nz - 1) - z : Mz - z;
                 src = cb + uint64_t(z) * es;
             } else {         // tap slot: kernel plane (s - NSP) - KC + kc, clamped (zeroed at use)
                 const int q = min(max(s - NSP - KC + kc, 0), 2 * kc);

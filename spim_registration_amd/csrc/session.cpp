@@ -464,6 +464,7 @@ void Session::build_spectra() {
             sl.C2.alloc(ne);
             SD_HIP(hipMemsetAsync(sl.C1.p, 0, sl.C1.bytes(), stream_));
             SD_HIP(hipMemsetAsync(sl.C2.p, 0, sl.C2.bytes(), stream_));
+            sl.c2_ext_valid = false;
             sl.e1spec.clear();
             sl.e2spec.clear();
             // compact kernels (2cz+1 z-planes, z transform in the z pass) unless
@@ -1103,10 +1104,32 @@ void Session::run_engine(int gi, int iters, double lambda, HostBarrier* bar) {
             exchange(buffer_a, st);
         }
     };
-    auto convolve = [&](SlabState& sl, float2* Cb, const float2* K, bool fwd_done) {
-        if (!fwd_done) { T0(2); engine_ypass(sl.sp, Cb, false, st); T1(); }
+    // A slab without neighbours leaves out its z-extension planes [nz, Mz):
+    // ext1 -- C1: they mirror interior planes, bit for bit; no pass writes them and the z
+    //         pass reads the planes they mirror (SPIMDECON_EXT_C1=0: computed as before);
+    // ext2 -- C2: the y spectra of the constant 1, the same for every view; after one whole
+    //         pass they stay where they are, no later pass touching them (SPIMDECON_EXT_C2=0).
+    // Slabs with neighbours hold exchanged halo planes there and keep every pass whole.
+    std::vector<char> ext1(slabs_.size(), 0), ext2(slabs_.size(), 0);
+    for (int s = s0; s < s1 && !halo; ++s) {
+        const SlabState& sl = slabs_[s];
+        const bool ok = sl.zexact && sl.kcompact && engine_ext_planes_ok(sl.sp);
+        ext1[s] = ok && sl.sp.knobs.ext_c1 && engine_zmirror_ok(sl.sp);
+        ext2[s] = ok && sl.sp.knobs.ext_c2;
+        // the update's partials of the tiles left out: zero, as those tiles would write them
+        if (ext1[s]) SD_HIP(hipMemsetAsync(sl.partials.p, 0, sl.partials.bytes(), st));
+    }
+    auto interior = [&](const SlabState& sl, bool prefix) {
+        PairRanges r = interior_pairs(sl.sp);
+        if (prefix) r.full = all_pairs(sl.sp).n0;
+        return r;
+    };
+    // yplanes >= 0: the forward y pass covers that many planes; zmir: mirrored z loads
+    auto convolve = [&](SlabState& sl, float2* Cb, const float2* K, bool fwd_done, int yplanes = -1,
+                        bool zmir = false) {
+        if (!fwd_done) { T0(2); engine_ypass(sl.sp, Cb, false, st, yplanes); T1(); }
         T0(3);
-        if (sl.kcompact) engine_zpass_compact(sl.sp, Cb, K, st);
+        if (sl.kcompact) engine_zpass_compact(sl.sp, Cb, K, st, zmir);
         else engine_zpass(sl.sp, Cb, K, st);
         T1();
         T0(2); engine_ypass(sl.sp, Cb, true, st); T1();
@@ -1146,12 +1169,19 @@ void Session::run_engine(int gi, int iters, double lambda, HostBarrier* bar) {
             return;
         }
         if (pending) xend();
-        for (int s = s0; s < s1; ++s) convolve(slabs_[s], buf(slabs_[s]), ker(slabs_[s]), false);
+        for (int s = s0; s < s1; ++s) {
+            SlabState& sl = slabs_[s];
+            const bool skip = buffer_a ? bool(ext1[s]) : (ext2[s] && sl.c2_ext_valid);
+            convolve(sl, buf(sl), ker(sl), false, skip ? int(sl.g.nz) : -1, buffer_a && ext1[s]);
+            // C2 after a whole forward y pass: its extension planes are in place
+            if (!buffer_a && ext2[s]) sl.c2_ext_valid = true;
+        }
     };
 
     for (int s = s0; s < s1; ++s) {
         T0(4);
-        engine_forward_psi(slabs_[s].sp, slabs_[s].psi, slabs_[s].C1.p, st);
+        const PairRanges ip = ext1[s] ? interior(slabs_[s], false) : all_pairs(slabs_[s].sp);
+        engine_forward_psi(slabs_[s].sp, slabs_[s].psi, slabs_[s].C1.p, st, &ip);
         T1();
     }
     xfull(true);
@@ -1199,7 +1229,8 @@ void Session::run_engine(int gi, int iters, double lambda, HostBarrier* bar) {
                 for (int s = s0; s < s1; ++s) {
                     SlabState& sl = slabs_[s];
                     T0(1);
-                    engine_quotient(sl.sp, store_, qin(sl), sl.img[v].p, qout(sl), all_pairs(sl.sp), st);
+                    engine_quotient(sl.sp, store_, qin(sl), sl.img[v].p, qout(sl),
+                                    ext2[s] && sl.c2_ext_valid ? interior(sl, false) : all_pairs(sl.sp), st);
                     T1();
                 }
                 xfull(false);
@@ -1219,7 +1250,8 @@ void Session::run_engine(int gi, int iters, double lambda, HostBarrier* bar) {
                 SlabState& sl = slabs_[s];
                 if (!ovc) T0(0);
                 nb[s] = engine_update(sl.sp, store_, sl.C2.p, sl.psi, sl.w[v].p, lambda, sl.psi_next,
-                                      last ? nullptr : sl.C1.p, sl.partials.p, ov ? bnd[s] : all_pairs(sl.sp),
+                                      last ? nullptr : sl.C1.p, sl.partials.p,
+                                      ov ? bnd[s] : ext1[s] ? interior(sl, true) : all_pairs(sl.sp),
                                       ovc ? gr.xstream : st);
                 if (!ovc) T1();
             }

@@ -54,6 +54,10 @@ struct SlabState {
     std::vector<DBuf<float2>> e1spec, e2spec;  // full kernel spectra, or compact ones (kcompact)
     bool kcompact = false;
     bool zexact = false;  // Mz = nz + 2 cz (direct z pass, no z FFT plan)
+    // C2's planes [nz, Mz) hold the y spectra of the quotient's constant-1 extension (the
+    // same for every view and iteration): true after a whole quotient pass and its forward
+    // y pass of a slab without neighbours, false once C2 is allocated anew (run_engine)
+    bool c2_ext_valid = false;
     DBuf<double> partials;
     DBuf<const void*> img_ptrs;
     std::unique_ptr<FftPlan3D> fft;
