@@ -412,6 +412,37 @@ int spim_dom_interest_points(const float* img, const int64_t* dims, const spim_d
                              int64_t* nout);
 
 /* ======================================================================
+ * 6b'. Downsampling in front of the detectors ("Downsample_XY" / "Downsample_Z") --
+ *     spim/process/interestpointdetection/Downsample.java:65-162 (simple2x along one axis),
+ *     spim/fiji/plugin/interestpointdetection/DifferenceOf.java:446-535 (openAndDownsample:
+ *     every x level, then y, then z; each level stored as float), :430-444 (downsampleFactor).
+ *     A line of n voxels becomes n / 2: out[0] = (in[0] + in[1] * 0.5) / 1.5,
+ *     out[q] = (in[2q-1] * 0.5 + in[2q] + in[2q+1] * 0.5) / 2.0, out[m-1] = (in[2m-2] +
+ *     in[2m-3] * 0.5) / 1.5, in double, rounded to float once per level.  Output voxel p is
+ *     centred on input voxel factor * p: detections scale back by the factor alone
+ *     (correctForDownsampling, :402-428).  Bit-exact against the reference's arithmetic.
+ * ====================================================================== */
+/* out_dims[a] = dims[a] halved (integer division) once per level of factor[a]; dims and
+ * factor in x, y, z order.  SPIMDECON_ERR_ARG for a factor outside {1, 2, 4, 8} or a level
+ * whose input is shorter than 4 on a downsampled axis (the reference reads out of bounds
+ * there).  Host only: needs no GPU. */
+int spim_downsample_dims(const int64_t dims[3], const int32_t factor[3], int64_t out_dims[3]);
+
+/* The downsampled view into out (sized by spim_downsample_dims).  Host or device pointers
+ * (as spim_dom_*); img is not modified; factor (1, 1, 1) copies.  The x and y chains of a
+ * plane are one kernel, the z chain a second one over the xy-reduced image, which lives in
+ * the workspace of spim_dog_release_workspace. */
+int spim_downsample(const float* img, const int64_t dims[3], const int32_t factor[3], int device,
+                    float* out);
+
+/* The xy factor of "Match Z Resolution (less downsampling)" (more = 0: 2^floor) and
+ * "(more downsampling)" (more != 0: 2^ceil) of log2(voxel[2] * ds_z / min(voxel[0], voxel[1])),
+ * rounded as the reference does.  Deliberate deviation: a result below 1 (a z step finer than
+ * xy; the reference returns 0 and scales every coordinate by 0) is 1.  A result above 8 (the
+ * reference's fixed choices end there) and a bad argument are SPIMDECON_ERR_ARG.  Host only. */
+int spim_downsample_factor_xy(int more, int32_t ds_z, const double voxel[3], int32_t* factor);
+
+/* ======================================================================
  * 6c. Descriptor-based pairwise registration, candidate stage: "redundant geometric local
  *     descriptor matching" (translation invariant) --
  *     spim/process/interestpointregistration/geometricdescriptor/RGLDMMatcher.java:44-123,

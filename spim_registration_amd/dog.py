@@ -42,7 +42,8 @@ def compute(img: np.ndarray, sigma: float = 1.8, threshold: float = 0.008, local
             image_sigma=(0.5, 0.5, 0.5), find_min: bool = False, find_max: bool = True,
             min_intensity: float = float("nan"), max_intensity: float = float("nan"),
             keep_intensity: bool = False, device: int | None = None, ij_threads: int = 8,
-            return_dog: bool = False, max_peaks: int | None = None, extension: str = "mirror"):
+            return_dog: bool = False, max_peaks: int | None = None, extension: str = "mirror",
+            downsample_xy: int = 1, downsample_z: int = 1):
     """ProcessDOG.compute: returns the list of InterestPoint (and the DoG image
     when ``return_dog``).  ``img`` is a [z, y, x] float32 volume (not modified):
     a numpy array, or a torch tensor on the GPU -- a view already resident in HBM
@@ -50,8 +51,18 @@ def compute(img: np.ndarray, sigma: float = 1.8, threshold: float = 0.008, local
     ``device``: the GPU that runs the pass; default the tensor's own GPU (device 0 for
     a host array).  ``extension``: how the Gaussians see beyond the image -- 'mirror'
     (the reference's accurate GPU mode) or 'border' (its approximate one: the edge voxel
-    repeated, DifferenceOfGaussianCUDA.java:125-148)."""
+    repeated, DifferenceOfGaussianCUDA.java:125-148).  ``downsample_xy`` / ``downsample_z``
+    (1, 2, 4 or 8): detect on the downsampled view (``downsample.downsample``; the
+    normalisation sees its min and max, ``sigma`` applies at its scale, the returned DoG
+    image has its size) and return positions in pixels of the full view."""
     ext = _extension(extension)
+    if (downsample_xy, downsample_z) != (1, 1):
+        from . import downsample as ds
+        res = compute(ds.downsample(img, downsample_xy, downsample_z, device=device), sigma, threshold,
+                      localization, image_sigma, find_min, find_max, min_intensity, max_intensity,
+                      keep_intensity, device, ij_threads, return_dog, max_peaks, extension)
+        _correct_points(res[0] if return_dog else res, downsample_xy, downsample_z)
+        return res
     lib = _lib.load()
     on_dev = hasattr(img, "is_cuda") and img.is_cuda
     if device is None:
@@ -96,6 +107,15 @@ def compute(img: np.ndarray, sigma: float = 1.8, threshold: float = 0.008, local
         out.append(InterestPoint(i, (ip.pos[0], ip.pos[1], ip.pos[2]),
                                  float(ip.intensity) if keep_intensity else None))
     return (out, dog) if return_dog else out
+
+
+def _correct_points(points, xy, z):
+    """correctForDownsampling on a list of InterestPoint, in place."""
+    if points:
+        from . import downsample as ds
+        loc = ds.correct_for_downsampling([p.location for p in points], xy, z)
+        for p, l in zip(points, loc):
+            p.location = tuple(l.tolist())
 
 
 def _params(lib, sigma, threshold, localization, image_sigma, find_min, find_max, min_intensity, max_intensity,
@@ -152,14 +172,22 @@ def _compute_device(lib, img, sigma, threshold, localization, image_sigma, find_
 def interest_points_array(img, sigma: float = 1.8, threshold: float = 0.008, localization: int = 0,
                           image_sigma=(0.5, 0.5, 0.5), find_min: bool = False, find_max: bool = True,
                           min_intensity: float = float("nan"), max_intensity: float = float("nan"),
-                          device: int | None = None, ij_threads: int = 8, extension: str = "mirror"):
+                          device: int | None = None, ij_threads: int = 8, extension: str = "mirror",
+                          downsample_xy: int = 1, downsample_z: int = 1):
     """ProcessDOG.compute on a GPU tensor, as arrays: (positions (n, 3) x, y, z;
     intensities (n,)) in the reference's order -- no per-point Python objects.
-    ``device`` defaults to the tensor's own GPU; ``extension`` as in ``compute``."""
+    ``device`` defaults to the tensor's own GPU; ``extension``, ``downsample_xy`` and
+    ``downsample_z`` as in ``compute``."""
     ext = _extension(extension)
     lib = _lib.load()
     if device is None:
         device = img.device.index
+    if (downsample_xy, downsample_z) != (1, 1):
+        from . import downsample as ds
+        pos, inten = interest_points_array(ds.downsample(img, downsample_xy, downsample_z, device=device), sigma,
+                                           threshold, localization, image_sigma, find_min, find_max,
+                                           min_intensity, max_intensity, device, ij_threads, extension)
+        return ds.correct_for_downsampling(pos, downsample_xy, downsample_z), inten
     img = img.contiguous().float()
     p = _params(lib, sigma, threshold, localization, image_sigma, find_min, find_max, min_intensity,
                 max_intensity, device, ij_threads)

@@ -85,13 +85,25 @@ def compute(img, radius1: int = 2, radius2: int = 3, threshold: float = 0.02, lo
             image_sigma=(0.5, 0.5, 0.5), find_min: bool = False, find_max: bool = True,
             min_intensity: float = float("nan"), max_intensity: float = float("nan"),
             keep_intensity: bool = False, device: int | None = None, ij_threads: int = 8,
-            return_dom: bool = False, max_peaks: int | None = None):
+            return_dom: bool = False, max_peaks: int | None = None, downsample_xy: int = 1,
+            downsample_z: int = 1):
     """ProcessDOM.compute: returns the list of InterestPoint (and the DOM image when
     ``return_dom``).  ``img`` is a [z, y, x] float32 volume (not modified, not
     normalised): a numpy array, or a torch tensor on the GPU -- a view already resident in
     HBM is read in place (the returned DOM image is then a torch tensor too).  ``device``:
     the GPU that runs the pass; default the tensor's own GPU (device 0 for a host array).
-    The threshold is used as given with either localization (ProcessDOM.java:104)."""
+    The threshold is used as given with either localization (ProcessDOM.java:104).
+    ``downsample_xy`` / ``downsample_z`` (1, 2, 4 or 8): detect on the downsampled view
+    (``downsample.downsample``; min, max and the returned DOM image are the downsampled
+    view's) and return positions in pixels of the full view."""
+    if (downsample_xy, downsample_z) != (1, 1):
+        from . import downsample as ds
+        from .dog import _correct_points
+        res = compute(ds.downsample(img, downsample_xy, downsample_z, device=device), radius1, radius2,
+                      threshold, localization, image_sigma, find_min, find_max, min_intensity, max_intensity,
+                      keep_intensity, device, ij_threads, return_dom, max_peaks)
+        _correct_points(res[0] if return_dom else res, downsample_xy, downsample_z)
+        return res
     on_dev = hasattr(img, "is_cuda") and img.is_cuda
     if device is None:
         device = img.device.index if on_dev else 0
@@ -108,9 +120,17 @@ def compute(img, radius1: int = 2, radius2: int = 3, threshold: float = 0.02, lo
 def interest_points_array(img, radius1: int = 2, radius2: int = 3, threshold: float = 0.02, localization: int = 0,
                           image_sigma=(0.5, 0.5, 0.5), find_min: bool = False, find_max: bool = True,
                           min_intensity: float = float("nan"), max_intensity: float = float("nan"),
-                          device: int | None = None, ij_threads: int = 8):
+                          device: int | None = None, ij_threads: int = 8, downsample_xy: int = 1,
+                          downsample_z: int = 1):
     """ProcessDOM.compute as arrays: (positions (n, 3) x, y, z; intensities (n,)) in the
-    reference's order -- no per-point Python objects.  ``device`` as in ``compute``."""
+    reference's order -- no per-point Python objects.  ``device``, ``downsample_xy`` and
+    ``downsample_z`` as in ``compute``."""
+    if (downsample_xy, downsample_z) != (1, 1):
+        from . import downsample as ds
+        pos, inten = interest_points_array(ds.downsample(img, downsample_xy, downsample_z, device=device), radius1,
+                                           radius2, threshold, localization, image_sigma, find_min, find_max,
+                                           min_intensity, max_intensity, device, ij_threads)
+        return ds.correct_for_downsampling(pos, downsample_xy, downsample_z), inten
     on_dev = hasattr(img, "is_cuda") and img.is_cuda
     if device is None:
         device = img.device.index if on_dev else 0

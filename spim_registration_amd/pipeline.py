@@ -117,7 +117,10 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
                       difference_threshold: float = 50.0, max_epsilon: float = 5.0,
                       min_inlier_ratio: float = 0.1, min_inlier_factor: float = 3.0,
                       num_iterations: int = 1000, ransac_seed: int | None = None, icp: bool = False,
-                      icp_max_distance: float = 5.0, icp_max_iterations: int = 100) -> TimepointResult:
+                      icp_max_distance: float = 5.0, icp_max_iterations: int = 100,
+                      downsample_xy=1, downsample_z: int = 1, voxel_size=None,
+                      max_detections: int | None = None,
+                      max_detections_type: str = "brightest") -> TimepointResult:
     """views: per view a [z, y, x] float32 torch tensor on the GPU (the acquired
     stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z);
     dog_extension: the detect stage's 'mirror' (accurate) or 'border' (approximate) GPU
@@ -132,8 +135,20 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
     default, 3 for RGLDM and 10 for geometric hashing; icp (needs ``refine``): after that
     matching's global optimisation, ``registration.register_icp`` with model ``refine``,
     icp_max_distance and icp_max_iterations on the models it produced -- the reference's ICP
-    run after a descriptor-based one; ``globalopt`` of the result then is the ICP run's."""
+    run after a descriptor-based one; ``globalopt`` of the result then is the ICP run's;
+    downsample_xy (1, 2, 4, 8, or 'match_z_less' / 'match_z_more', which need voxel_size
+    (x, y, z)) and downsample_z: the detect stage runs on the downsampled views
+    (``downsample.downsample``, DifferenceOf.openAndDownsample) and ``points`` are corrected to
+    pixels of the full views, so every later stage is untouched; ``ms["downsample"]`` is that
+    pass alone and is part of ``ms["detect"]``; max_detections / max_detections_type
+    ('brightest', 'median', 'weakest'): ``downsample.limit_detections`` per view."""
     import torch
+    from . import downsample as ds
+    ds_z = ds.downsample_factor(downsample_z)
+    ds_xy = ds.downsample_factor(downsample_xy, ds_z, voxel_size)
+    if max_detections_type not in ds.LIMIT_KINDS:
+        raise ValueError(f"max_detections_type must be 'brightest', 'median' or 'weakest', not "
+                         f"{max_detections_type!r}")
     if icp and refine is None:
         raise ValueError("icp=True needs refine (the model of the ICP registration)")
     if detector not in ("dog", "dom"):
@@ -152,14 +167,27 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
     torch.cuda.synchronize(device)
     t = time.perf_counter()
     points = []
+    t_ds = 0.0
     for v in views:          # 1. ProcessDOG (or ProcessDOM) per view, read in place
+        if (ds_xy, ds_z) != (1, 1):   # (the call returns after its stream has drained)
+            t0 = time.perf_counter()
+            v = ds.downsample(v, ds_xy, ds_z, device=device)
+            t_ds += time.perf_counter() - t0
         if detector == "dom":
-            pos, _ = dom.interest_points_array(v, radius1=radius1, radius2=radius2, threshold=threshold,
-                                               localization=localization, device=device)
+            pos, inten = dom.interest_points_array(v, radius1=radius1, radius2=radius2, threshold=threshold,
+                                                   localization=localization, device=device)
         else:
-            pos, _ = dog.interest_points_array(v, sigma=sigma, threshold=threshold, localization=localization,
-                                               device=device, extension=dog_extension)
+            pos, inten = dog.interest_points_array(v, sigma=sigma, threshold=threshold,
+                                                   localization=localization, device=device,
+                                                   extension=dog_extension)
+        if (ds_xy, ds_z) != (1, 1):
+            pos = ds.correct_for_downsampling(pos, ds_xy, ds_z)
+        if max_detections is not None:
+            pos, _ = ds.limit_detections(pos, inten, max_detections, max_detections_type)
+            pos = np.ascontiguousarray(pos)
         points.append(pos)
+    if (ds_xy, ds_z) != (1, 1):
+        ms["downsample"] = round(t_ds * 1e3, 2)
     t = lap("detect", t)
     gres = None
     models = [np.asarray(m, np.float64).reshape(3, 4) for m in models]
