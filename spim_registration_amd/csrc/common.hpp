@@ -7,6 +7,9 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -43,6 +46,9 @@ void clear_last_error();
 
 // Validates a device id (>= 0 and present).  There is no CPU fallback.
 void check_device(int dev);
+
+// true when p is device memory of `dev` itself
+bool is_device_ptr(const void* p, int dev);
 
 // Scoped hipSetDevice with restore.
 struct DeviceGuard {
@@ -84,6 +90,37 @@ struct DBuf {
     }
     size_t bytes() const { return n * sizeof(T); }
 };
+
+// a workspace buffer: grown on demand, never shrunk (the contents do not survive growing)
+template <typename T>
+void grow(DBuf<T>& b, size_t n) {
+    if (b.n < n) b.alloc(n);
+}
+
+// The W of every device that has asked for one, held under the lock.  The map is never
+// destroyed (as legacy.cpp's g_ctx): no hipFree / hipStreamDestroy from a static destructor
+// racing the HIP runtime's own teardown at process exit.
+template <class W>
+struct PerDevice {
+    std::unique_lock<std::mutex> lock;
+    std::map<int, std::unique_ptr<W>>& by_dev;
+};
+template <class W>
+PerDevice<W> per_device_all() {
+    static std::mutex mu;
+    static auto& by_dev = *new std::map<int, std::unique_ptr<W>>();
+    return {std::unique_lock<std::mutex>(mu), by_dev};
+}
+
+// Device dev's W -- a workspace with its own mutex, stream and buffers --, made on first use
+// and kept between calls.
+template <class W>
+W& per_device(int dev) {
+    PerDevice<W> all = per_device_all<W>();
+    auto& w = all.by_dev[dev];
+    if (!w) w.reset(new W());
+    return *w;
+}
 
 // Runs fn() converting exceptions to status codes + last-error message.
 template <typename F>

@@ -1622,31 +1622,8 @@ int dog_env(const char* name, int def) {
     return v && *v ? std::atoi(v) : def;
 }
 
-// true when p is device memory of `dev` itself (read / written in place by its kernels);
-// host memory and other devices' buffers are staged through the workspace instead (a
-// kernel on dev would fault on another device's memory without peer access)
-bool is_device_ptr(const void* p, int dev) {
-    if (!p) return false;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();   // pageable host memory: not registered with HIP
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == dev;
-}
-
 // (the per-device workspace DogWork: dog_detect.hpp)
-std::mutex g_dogwork_mu;
-// never destroyed (as legacy.cpp's g_ctx): no hipFree / hipStreamDestroy from a static
-// destructor racing the HIP runtime's own teardown at process exit
-std::map<int, std::unique_ptr<DogWork>>& g_dogwork = *new std::map<int, std::unique_ptr<DogWork>>();
-
-DogWork& dog_work(int dev) {
-    std::lock_guard<std::mutex> lk(g_dogwork_mu);
-    auto& w = g_dogwork[dev];
-    if (!w) w.reset(new DogWork());
-    return *w;
-}
+DogWork& dog_work(int dev) { return per_device<DogWork>(dev); }
 
 int bits_for(uint64_t v) {
     int b = 0;

@@ -5,8 +5,6 @@
 // both detectors.
 #pragma once
 
-#include <mutex>
-
 #include "common.hpp"
 
 namespace spimdecon {
@@ -79,11 +77,6 @@ struct DogWork {
 
 DogWork& dog_work(int dev);
 
-template <typename T>
-void grow(DBuf<T>& b, size_t n) {
-    if (b.n < n) b.alloc(n);
-}
-
 struct StreamHolder {   // the workspace's stream (held under its mutex)
     hipStream_t s = nullptr;
     explicit StreamHolder(DogWork& w) : s(w.get_stream()) {}
@@ -96,9 +89,6 @@ struct DogRun {
     int64_t np = 0;
     const PeakOut* dpeaks = nullptr;
 };
-
-// true when p is device memory of `dev` itself
-bool is_device_ptr(const void* p, int dev);
 
 // InteractiveIntegral.findPeaks over a stored device image: the extrema with
 // |v| >= min_peak of the wanted kinds, in the reference's order, into r.np / r.dpeaks

@@ -18,21 +18,19 @@
 // reference ranks B descriptors with fiji.util.KDTree (not in its tree); here by
 // (float) Math.sqrt(descriptorDistance) ascending, equal floats by lower B index, a NaN distance
 // not ranked.
-//   k_rgldm_knn<3>    (rgldm.hip) per point the 3 nearest others, neighbour - basis in double
+//   k_pm_knn<3>       (pointmatch.hip) per point the 3 nearest others, neighbour - basis in double
 //   k_gh_descriptors  one thread per point: x / y / n axes, 3x3 LU inverse, (ax bx by cx cy cz) float
 //   k_gh_match        a lane owns one A descriptor in registers; B descriptors go through LDS in
 //                     tiles and are read as broadcasts; grid.y splits B (partial two best)
 //   k_gh_merge        partials in ascending B order -> two best by (key, index); the two tests
-//   k_rgldm_compact   (rgldm.hip) the candidates in ascending A order
+//   k_pm_compact      (pointmatch.hip) the candidates in ascending A order
+// The call around them -- argument rules, staging, "not enough detections", the result copies --
+// is pm_match_candidates (pointmatch.hpp), shared with rgldm.hip.
 // No atomics; every output is written with ordinary stores.
 #include <algorithm>
 #include <cfloat>
-#include <map>
-#include <memory>
-#include <mutex>
 
-#include "common.hpp"
-#include "rgldm.hpp"
+#include "pointmatch.hpp"
 
 namespace spimdecon {
 namespace {
@@ -41,7 +39,6 @@ constexpr int kGhATile = 256;    // A descriptors (lanes) per block of k_gh_matc
 constexpr int kGhBTile = 256;    // B descriptors per LDS tile
 constexpr int kGhBlock = 256;
 constexpr int kGhMinPoints = 4;  // GeometricHashingPairwise.java:58
-constexpr double kJavaDoubleMax = DBL_MAX;
 
 struct GhVec {
     double x, y, z;
@@ -312,56 +309,22 @@ __global__ __launch_bounds__(kGhBlock) void k_gh_merge(int na, int nparts, const
     flag[i] = (two && best < thr && __dmul_rn(best, ratio) <= second) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(kGhBlock) void k_gh_fill(int na, double* __restrict__ best, double* __restrict__ second,
-                                                      int* __restrict__ idx) {
-    const int i = int(blockIdx.x) * kGhBlock + int(threadIdx.x);
-    if (i >= na) return;
-    best[i] = kJavaDoubleMax;
-    second[i] = kJavaDoubleMax;
-    idx[i] = -1;
-}
-
-// Per-device workspace, grown on demand and kept between calls (never destroyed, as rgldm.hip's).
-struct GhWork {
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    DBuf<double> pts_a, pts_b, rel, pd1, pd2, best, second;
+// Per-device workspace, grown on demand and kept between calls.
+struct GhWork : PmCandidateWork {
+    DBuf<double> rel, pd1, pd2;
     DBuf<float> desc_a, desc_b;
-    DBuf<int> nbr, pi1, pi2, idx, cand_a, cand_b, bad;
-    DBuf<unsigned char> flag;
-    DBuf<int64_t> count;
-    hipStream_t get_stream() {
-        if (!stream) SD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        return stream;
-    }
+    DBuf<int> nbr, pi1, pi2;
 };
-std::mutex g_ghwork_mu;
-std::map<int, std::unique_ptr<GhWork>>& g_ghwork = *new std::map<int, std::unique_ptr<GhWork>>();
-GhWork& gh_work(int dev) {
-    std::lock_guard<std::mutex> lk(g_ghwork_mu);
-    auto& w = g_ghwork[dev];
-    if (!w) w.reset(new GhWork());
-    return *w;
-}
-template <typename T>
-void gh_grow(DBuf<T>& b, size_t n) {
-    if (b.n < n) b.alloc(n);
-}
 
 void gh_check_params(const spim_gh_params* p) {
     SD_CHECK(p, SPIMDECON_ERR_ARG, "null argument");
     SD_CHECK(p->b_split >= 0, SPIMDECON_ERR_ARG, "geometric hashing: b_split must be >= 0");
 }
 
-void gh_check_count(const double* pts, int64_t n) {
-    SD_CHECK(n >= 0 && (pts || n == 0), SPIMDECON_ERR_ARG, "null argument");
-    SD_CHECK(n <= int64_t(INT32_MAX), SPIMDECON_ERR_ARG, "geometric hashing: more than 2^31 - 1 points");
-}
-
 // neighbours (w.nbr, w.rel) and the descriptors of n >= 4 staged points into desc
 void gh_describe(const double* dpts, int n, GhWork& w, float* desc, hipStream_t s) {
-    gh_grow(w.nbr, size_t(n) * 3);
-    gh_grow(w.rel, size_t(n) * 9);
+    grow(w.nbr, size_t(n) * 3);
+    grow(w.rel, size_t(n) * 9);
     pm_knn(dpts, n, 3, w.nbr.p, w.rel.p, s);
     hipLaunchKernelGGL(k_gh_descriptors, dim3(unsigned(ceil_div(n, kGhBlock))), dim3(kGhBlock), 0, s, w.rel.p, n,
                        desc);
@@ -370,16 +333,16 @@ void gh_describe(const double* dpts, int n, GhWork& w, float* desc, hipStream_t 
 
 void gh_descriptors(const double* pts, int64_t n, const spim_gh_params* p, int32_t* neighbors, float* desc) {
     gh_check_params(p);
-    gh_check_count(pts, n);
+    pm_check_points(pts, n, "geometric hashing");
     SD_CHECK(neighbors && desc, SPIMDECON_ERR_ARG, "null argument");
     SD_CHECK(n >= kGhMinPoints, SPIMDECON_ERR_ARG, "geometric hashing: a descriptor needs 4 points");
     check_device(p->device);
     DeviceGuard guard(p->device);
-    GhWork& w = gh_work(p->device);
+    GhWork& w = per_device<GhWork>(p->device);
     std::lock_guard<std::mutex> lk(w.mu);
     hipStream_t s = w.get_stream();
     const double* d = pm_stage_points(pts, n, p->device, w.pts_a, w.bad, s, "geometric hashing");
-    gh_grow(w.desc_a, size_t(n) * 6);
+    grow(w.desc_a, size_t(n) * 6);
     gh_describe(d, int(n), w, w.desc_a.p, s);
     SD_HIP(hipMemcpyAsync(neighbors, w.nbr.p, size_t(n) * 3 * sizeof(int), hipMemcpyDefault, s));
     SD_HIP(hipMemcpyAsync(desc, w.desc_a.p, size_t(n) * 6 * sizeof(float), hipMemcpyDefault, s));
@@ -389,75 +352,29 @@ void gh_descriptors(const double* pts, int64_t n, const spim_gh_params* p, int32
 void gh_match(const double* a, int64_t na, const double* b, int64_t nb, const spim_gh_params* p, int32_t* best_idx,
               double* best, double* second, int32_t* cand_a, int32_t* cand_b, int64_t cap, int64_t* count) {
     gh_check_params(p);
-    gh_check_count(a, na);
-    gh_check_count(b, nb);
-    SD_CHECK(count && cap >= 0 && (cap == 0 || (cand_a && cand_b)), SPIMDECON_ERR_ARG, "null argument");
-    SD_CHECK(na == 0 || (best_idx && best && second), SPIMDECON_ERR_ARG, "null argument");
-    *count = 0;
-    check_device(p->device);
-    DeviceGuard guard(p->device);
-    GhWork& w = gh_work(p->device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    hipStream_t s = w.get_stream();
-    const double* da = na ? pm_stage_points(a, na, p->device, w.pts_a, w.bad, s, "geometric hashing") : nullptr;
-    const double* db = nb ? pm_stage_points(b, nb, p->device, w.pts_b, w.bad, s, "geometric hashing") : nullptr;
-    if (na == 0) return;
-    gh_grow(w.best, size_t(na));
-    gh_grow(w.second, size_t(na));
-    gh_grow(w.idx, size_t(na));
-    const unsigned ga = unsigned(ceil_div(na, kGhBlock));
-    if (na < kGhMinPoints || nb < kGhMinPoints) {
-        // GeometricHashingPairwise.java:58-65, "Not enough detections to match": no candidates
-        hipLaunchKernelGGL(k_gh_fill, dim3(ga), dim3(kGhBlock), 0, s, int(na), w.best.p, w.second.p, w.idx.p);
-        SD_HIP(hipGetLastError());
-    } else {
-        gh_grow(w.desc_a, size_t(na) * 6);
-        gh_grow(w.desc_b, size_t(nb) * 6);
-        gh_describe(da, int(na), w, w.desc_a.p, s);
-        gh_describe(db, int(nb), w, w.desc_b.p, s);
-        // B split: 16,000 A descriptors are 63 blocks; aim at 2 blocks of 4 waves per CU
-        const int64_t ablocks = ceil_div(na, kGhATile);
-        int64_t split = p->b_split;
-        if (split <= 0) {
-            int cus = 0;
-            SD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
-            const int64_t want = int64_t(cus) * 2;
-            split = std::min<int64_t>(std::max<int64_t>(ceil_div(want, ablocks), 1), ceil_div(nb, kGhBTile));
-        }
-        split = std::min<int64_t>(split, 65535);
-        const int chunk = int(ceil_div(nb, split));
-        SD_CHECK(ablocks * split < (int64_t(1) << 31), SPIMDECON_ERR_ARG, "geometric hashing: too many blocks");
-        gh_grow(w.pd1, size_t(na) * split);
-        gh_grow(w.pd2, size_t(na) * split);
-        gh_grow(w.pi1, size_t(na) * split);
-        gh_grow(w.pi2, size_t(na) * split);
-        hipLaunchKernelGGL(k_gh_match, dim3(unsigned(ablocks), unsigned(split)), dim3(kGhATile), 0, s, w.desc_a.p,
-                           int(na), w.desc_b.p, int(nb), chunk, w.pd1.p, w.pd2.p, w.pi1.p, w.pi2.p);
-        SD_HIP(hipGetLastError());
-        gh_grow(w.flag, size_t(na));
-        hipLaunchKernelGGL(k_gh_merge, dim3(ga), dim3(kGhBlock), 0, s, int(na), int(split), w.pd1.p, w.pd2.p, w.pi1.p,
-                           w.pi2.p, p->difference_threshold, p->ratio_of_distance, w.best.p, w.second.p, w.idx.p,
-                           w.flag.p);
-        SD_HIP(hipGetLastError());
-        gh_grow(w.count, 1);
-        const int64_t dcap = std::min<int64_t>(cap, na);
-        gh_grow(w.cand_a, size_t(std::max<int64_t>(dcap, 1)));
-        gh_grow(w.cand_b, size_t(std::max<int64_t>(dcap, 1)));
-        pm_compact(int(na), w.flag.p, w.idx.p, w.cand_a.p, w.cand_b.p, dcap, w.count.p, s);
-        SD_HIP(hipMemcpyAsync(count, w.count.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    }
-    SD_HIP(hipMemcpyAsync(best_idx, w.idx.p, size_t(na) * sizeof(int), hipMemcpyDefault, s));
-    SD_HIP(hipMemcpyAsync(best, w.best.p, size_t(na) * sizeof(double), hipMemcpyDefault, s));
-    SD_HIP(hipMemcpyAsync(second, w.second.p, size_t(na) * sizeof(double), hipMemcpyDefault, s));
-    SD_HIP(hipStreamSynchronize(s));
-    SD_CHECK(*count <= cap, SPIMDECON_ERR_ARG,
-             "geometric hashing: " + std::to_string(*count) + " candidates beyond the capacity " +
-                 std::to_string(cap));
-    if (*count) {
-        SD_HIP(hipMemcpyAsync(cand_a, w.cand_a.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
-        SD_HIP(hipMemcpyAsync(cand_b, w.cand_b.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
-        SD_HIP(hipStreamSynchronize(s));
-    }
+    // fewer than 4 points: GeometricHashingPairwise.java:58-65, "Not enough detections to match": no candidates
+    pm_match_candidates<GhWork>(
+        "geometric hashing", kGhMinPoints, p->device, a, na, b, nb, best_idx, best, second, cand_a, cand_b, cap,
+        count, [&](GhWork& w, const double* da, const double* db, hipStream_t s) {
+            grow(w.desc_a, size_t(na) * 6);
+            grow(w.desc_b, size_t(nb) * 6);
+            gh_describe(da, int(na), w, w.desc_a.p, s);
+            gh_describe(db, int(nb), w, w.desc_b.p, s);
+            // B split: 16,000 A descriptors are 63 blocks; aim at 2 blocks of 4 waves per CU
+            const int64_t ablocks = ceil_div(na, kGhATile);
+            const PmSplit sp = pm_split(p->b_split, ablocks, nb, kGhBTile, 2, p->device, "geometric hashing");
+            grow(w.pd1, size_t(na) * sp.split);
+            grow(w.pd2, size_t(na) * sp.split);
+            grow(w.pi1, size_t(na) * sp.split);
+            grow(w.pi2, size_t(na) * sp.split);
+            hipLaunchKernelGGL(k_gh_match, dim3(unsigned(ablocks), unsigned(sp.split)), dim3(kGhATile), 0, s,
+                               w.desc_a.p, int(na), w.desc_b.p, int(nb), sp.chunk, w.pd1.p, w.pd2.p, w.pi1.p, w.pi2.p);
+            SD_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_gh_merge, dim3(unsigned(ceil_div(na, kGhBlock))), dim3(kGhBlock), 0, s, int(na),
+                               int(sp.split), w.pd1.p, w.pd2.p, w.pi1.p, w.pi2.p, p->difference_threshold,
+                               p->ratio_of_distance, w.best.p, w.second.p, w.idx.p, w.flag.p);
+            SD_HIP(hipGetLastError());
+        });
 }
 
 }  // namespace

@@ -14,28 +14,21 @@
 // (which never contracts a multiply and an add), so the nearest index, the float distance and
 // the match list are bit-exact against a restatement.  Unpinned: the reference searches with
 // fiji.util.KDTree (not in its tree); among equal float distances the lower target index wins
-// here, as in k_rgldm_knn.
+// here, as in k_pm_knn.
 //   k_icp_apply     one thread per target point: w = M l in double, three floats padded to 16 bytes
 //   k_icp_assign    a lane owns one reference point; the target floats go through LDS in tiles
 //                   and are read as broadcasts; grid.y splits the target (partial nearest)
 //   k_icp_merge     partials in ascending target order -> nearest, distance, the threshold;
 //                   per-target claim counts over the thresholded matches (integer atomics)
 //   k_icp_resolve   a match survives when its target is claimed once; counts the others
-//   k_rgldm_compact (rgldm.hip) the survivors in ascending reference order
+//   k_pm_compact    (pointmatch.hip) the survivors in ascending reference order
 // No kernel waits on another block; every loop is bounded by a count the host passes.
 #include <algorithm>
 #include <cfloat>
-#include <map>
-#include <memory>
-#include <mutex>
 
-#include "common.hpp"
-#include "rgldm.hpp"
+#include "pointmatch.hpp"
 
 namespace spimdecon {
-
-bool is_device_ptr(const void* p, int dev);   // dog.hip
-
 namespace {
 
 constexpr int kIcpRBlock = 256;    // reference points (lanes) per block of k_icp_assign
@@ -170,47 +163,24 @@ __global__ __launch_bounds__(kIcpBlock) void k_icp_fill(int nr, int* __restrict_
     dist[i] = FLT_MAX;
 }
 
-// Per-device workspace, grown on demand and kept between calls (never destroyed, as rgldm.hip's):
+// Per-device workspace, grown on demand and kept between calls:
 // the iterations of one pair, and the pairs of one timepoint, allocate once.
-struct IcpWork {
-    std::mutex mu;
-    hipStream_t stream = nullptr;
+struct IcpWork : PmWork {
     DBuf<double> pts_t, pts_r;
     DBuf<float4> tw;
     DBuf<float> pd, dist;
-    DBuf<int> pi, nearest, claims, match_t, match_r, bad;
+    DBuf<int> pi, nearest, claims, match_t, match_r;
     DBuf<unsigned char> matched, keep;
     DBuf<int64_t> stats;   // the matches, the ambiguous ones, the non-finite flag of k_icp_apply
-    hipStream_t get_stream() {
-        if (!stream) SD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        return stream;
-    }
 };
-std::mutex g_icpwork_mu;
-std::map<int, std::unique_ptr<IcpWork>>& g_icpwork = *new std::map<int, std::unique_ptr<IcpWork>>();
-IcpWork& icp_work(int dev) {
-    std::lock_guard<std::mutex> lk(g_icpwork_mu);
-    auto& w = g_icpwork[dev];
-    if (!w) w.reset(new IcpWork());
-    return *w;
-}
-template <typename T>
-void icp_grow(DBuf<T>& b, size_t n) {
-    if (b.n < n) b.alloc(n);
-}
-
-void icp_check_count(const double* pts, int64_t n) {
-    SD_CHECK(n >= 0 && (pts || n == 0), SPIMDECON_ERR_ARG, "null argument");
-    SD_CHECK(n <= int64_t(INT32_MAX), SPIMDECON_ERR_ARG, "icp: more than 2^31 - 1 points");
-}
 
 void icp_assign(const double* target, int64_t nt, const double* reference, int64_t nr, const double* model,
                 const spim_icp_params* p, int32_t* nearest, float* dist, int32_t* match_t, int32_t* match_r,
                 int64_t cap, int64_t* count, int64_t* ambiguous) {
     SD_CHECK(p, SPIMDECON_ERR_ARG, "null argument");
     SD_CHECK(p->t_split >= 0, SPIMDECON_ERR_ARG, "icp: t_split must be >= 0");
-    icp_check_count(target, nt);
-    icp_check_count(reference, nr);
+    pm_check_points(target, nt, "icp");
+    pm_check_points(reference, nr, "icp");
     SD_CHECK(count && ambiguous && cap >= 0 && (cap == 0 || (match_t && match_r)), SPIMDECON_ERR_ARG,
              "null argument");
     SD_CHECK(nr == 0 || (nearest && dist), SPIMDECON_ERR_ARG, "null argument");
@@ -218,7 +188,7 @@ void icp_assign(const double* target, int64_t nt, const double* reference, int64
     *ambiguous = 0;
     check_device(p->device);
     DeviceGuard guard(p->device);
-    IcpWork& w = icp_work(p->device);
+    IcpWork& w = per_device<IcpWork>(p->device);
     std::lock_guard<std::mutex> lk(w.mu);
     hipStream_t s = w.get_stream();
     IcpModel mdl = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
@@ -231,49 +201,40 @@ void icp_assign(const double* target, int64_t nt, const double* reference, int64
     const double* dt = nt ? pm_stage_points(target, nt, p->device, w.pts_t, w.bad, s, "icp") : nullptr;
     const double* dr = nr ? pm_stage_points(reference, nr, p->device, w.pts_r, w.bad, s, "icp") : nullptr;
     if (nr == 0) return;
-    icp_grow(w.nearest, size_t(nr));
-    icp_grow(w.dist, size_t(nr));
-    icp_grow(w.stats, 3);
+    grow(w.nearest, size_t(nr));
+    grow(w.dist, size_t(nr));
+    grow(w.stats, 3);
     SD_HIP(hipMemsetAsync(w.stats.p, 0, 3 * sizeof(int64_t), s));
     const unsigned gr = unsigned(ceil_div(nr, kIcpBlock));
     if (nt == 0) {
         hipLaunchKernelGGL(k_icp_fill, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), w.nearest.p, w.dist.p);
         SD_HIP(hipGetLastError());
     } else {
-        icp_grow(w.tw, size_t(nt));
+        grow(w.tw, size_t(nt));
         hipLaunchKernelGGL(k_icp_apply, dim3(unsigned(ceil_div(nt, kIcpBlock))), dim3(kIcpBlock), 0, s, dt, int(nt),
                            mdl, w.tw.p, w.stats.p + 2);
         SD_HIP(hipGetLastError());
         // target split: 16,000 reference points are 63 blocks; aim at 2 blocks of 4 waves per CU
         const int64_t rblocks = ceil_div(nr, kIcpRBlock);
-        int64_t split = p->t_split;
-        if (split <= 0) {
-            int cus = 0;
-            SD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
-            const int64_t want = int64_t(cus) * 2;
-            split = std::min<int64_t>(std::max<int64_t>(ceil_div(want, rblocks), 1), ceil_div(nt, kIcpTTile));
-        }
-        split = std::min<int64_t>(split, 65535);
-        const int chunk = int(ceil_div(nt, split));
-        SD_CHECK(rblocks * split < (int64_t(1) << 31), SPIMDECON_ERR_ARG, "icp: too many blocks");
-        icp_grow(w.pd, size_t(nr) * split);
-        icp_grow(w.pi, size_t(nr) * split);
-        hipLaunchKernelGGL(k_icp_assign, dim3(unsigned(rblocks), unsigned(split)), dim3(kIcpRBlock), 0, s, w.tw.p,
-                           int(nt), dr, int(nr), chunk, w.pd.p, w.pi.p);
+        const PmSplit sp = pm_split(p->t_split, rblocks, nt, kIcpTTile, 2, p->device, "icp");
+        grow(w.pd, size_t(nr) * sp.split);
+        grow(w.pi, size_t(nr) * sp.split);
+        hipLaunchKernelGGL(k_icp_assign, dim3(unsigned(rblocks), unsigned(sp.split)), dim3(kIcpRBlock), 0, s, w.tw.p,
+                           int(nt), dr, int(nr), sp.chunk, w.pd.p, w.pi.p);
         SD_HIP(hipGetLastError());
-        icp_grow(w.matched, size_t(nr));
-        icp_grow(w.keep, size_t(nr));
-        icp_grow(w.claims, size_t(nt));
+        grow(w.matched, size_t(nr));
+        grow(w.keep, size_t(nr));
+        grow(w.claims, size_t(nt));
         SD_HIP(hipMemsetAsync(w.claims.p, 0, size_t(nt) * sizeof(int), s));
-        hipLaunchKernelGGL(k_icp_merge, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), int(split), w.pd.p, w.pi.p,
+        hipLaunchKernelGGL(k_icp_merge, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), int(sp.split), w.pd.p, w.pi.p,
                            double(p->max_distance), w.nearest.p, w.dist.p, w.matched.p, w.claims.p);
         SD_HIP(hipGetLastError());
         hipLaunchKernelGGL(k_icp_resolve, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), w.nearest.p, w.matched.p,
                            w.claims.p, w.keep.p, w.stats.p);
         SD_HIP(hipGetLastError());
         const int64_t dcap = std::min<int64_t>(cap, nr);
-        icp_grow(w.match_t, size_t(std::max<int64_t>(dcap, 1)));
-        icp_grow(w.match_r, size_t(std::max<int64_t>(dcap, 1)));
+        grow(w.match_t, size_t(std::max<int64_t>(dcap, 1)));
+        grow(w.match_r, size_t(std::max<int64_t>(dcap, 1)));
         pm_compact(int(nr), w.keep.p, w.nearest.p, w.match_r.p, w.match_t.p, dcap, w.stats.p, s);
     }
     int64_t stats[3] = {0, 0, 0};

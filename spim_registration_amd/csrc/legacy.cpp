@@ -104,6 +104,19 @@ void check_device(int dev) {
                                        std::to_string(n) + " devices; negative = CPU is not supported)");
 }
 
+// true when p is device memory of `dev` itself (read / written in place by its kernels);
+// host memory and other devices' buffers are staged through the workspace instead (a
+// kernel on dev would fault on another device's memory without peer access)
+bool is_device_ptr(const void* p, int dev) {
+    if (!p) return false;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();   // pageable host memory: not registered with HIP
+        return false;
+    }
+    return at.type == hipMemoryTypeDevice && at.device == dev;
+}
+
 // In-place circular convolution of one block (see spimdecon.h).
 void fft_convolve_block(float* im, const int* imDim, const float* kernel, const int* kernelDim,
                         int dev, float* out) {

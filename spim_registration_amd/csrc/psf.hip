@@ -307,22 +307,10 @@ struct PsfWork {
     DBuf<float> dimg, dpsf, samp, dt;
     DBuf<double> dloc, mm;
 };
-template <typename T>
-void ensure(DBuf<T>& b, size_t n) {
-    if (b.n < n) b.alloc(n);
-}
 struct PsfPool {
     std::mutex mu;   // one extract call at a time per device
     std::vector<std::unique_ptr<PsfWork>> w;
 };
-std::mutex g_psf_pool_mu;
-std::map<int, std::unique_ptr<PsfPool>>& g_psf_pool = *new std::map<int, std::unique_ptr<PsfPool>>();
-PsfPool& psf_pool(int dev) {
-    std::lock_guard<std::mutex> lk(g_psf_pool_mu);
-    auto& p = g_psf_pool[dev];
-    if (!p) p.reset(new PsfPool());
-    return *p;
-}
 }  // namespace
 
 // One view's ExtractPSF.extract (:281-299) + transformPSF, in three steps so several
@@ -353,25 +341,25 @@ struct PsfJob {
         // buffers (grown, reused) and uploads (asynchronous on this job's stream)
         src = img;
         if (!img_on_device) {
-            ensure(w.dimg, s.n());
+            grow(w.dimg, s.n());
             SD_HIP(hipMemcpyAsync(w.dimg.p, img, s.n() * 4, hipMemcpyHostToDevice, w.st.s));
             src = w.dimg.p;
         }
-        ensure(w.dloc, size_t(std::max<int64_t>(nloc, 1)) * 3);
+        grow(w.dloc, size_t(std::max<int64_t>(nloc, 1)) * 3);
         if (nloc) SD_HIP(hipMemcpyAsync(w.dloc.p, locations, nloc * 24, hipMemcpyHostToDevice, w.st.s));
-        ensure(w.dpsf, p.n());
-        ensure(w.mm, 2);
+        grow(w.dpsf, p.n());
+        grow(w.mm, 2);
         if (nloc > 64) {   // bead chunks of <= 2^26 samples (256 MB), <= 65535 beads (grid.y)
             SD_CHECK(p.n() < (int64_t(1) << 31), SPIMDECON_ERR_ARG, "psf too large");
             chunk = std::max<int64_t>(1, std::min<int64_t>({nloc, (int64_t(1) << 26) / p.n(), int64_t(65535)}));
-            ensure(w.samp, size_t(chunk * p.n()));
+            grow(w.samp, size_t(chunk * p.n()));
         }
         if (psf_transformed) {
             int64_t ts[3];
             double off[3];
             transformed_size(psf_size, model, ts, off);
             tn = dim3_of(ts, "transformed psf").n();
-            ensure(w.dt, size_t(tn));
+            grow(w.dt, size_t(tn));
         }
     }
 
@@ -416,7 +404,7 @@ void extract_psf(const float* img, const int64_t* dims, int img_on_device, const
                  int device) {
     check_device(device);
     DeviceGuard guard(device);
-    PsfPool& pool = psf_pool(device);
+    PsfPool& pool = per_device<PsfPool>(device);
     std::lock_guard<std::mutex> lk(pool.mu);
     if (pool.w.empty()) pool.w.emplace_back(new PsfWork());
     PsfJob job(*pool.w[0], img, dims, img_on_device, locations, nloc, psf_size, model, psf_original, psf_transformed);
@@ -431,7 +419,7 @@ void extract_psfs(int nviews, const float* const* imgs, const int64_t* dims, int
              SPIMDECON_ERR_ARG, "null argument");
     check_device(device);
     DeviceGuard guard(device);
-    PsfPool& pool = psf_pool(device);
+    PsfPool& pool = per_device<PsfPool>(device);
     std::lock_guard<std::mutex> lk(pool.mu);
     while (int(pool.w.size()) < nviews) pool.w.emplace_back(new PsfWork());
     std::vector<std::unique_ptr<PsfJob>> jobs;
@@ -542,8 +530,8 @@ extern "C" int spim_extract_psfs(int nviews, const float* const* imgs, const int
 
 // frees the per-view buffers and streams extract_psf(s) keep on a device (-1: every device)
 void psf_release_workspace(int device) {
-    std::lock_guard<std::mutex> lk(g_psf_pool_mu);
-    for (auto& kv : g_psf_pool) {
+    PerDevice<PsfPool> all = per_device_all<PsfPool>();
+    for (auto& kv : all.by_dev) {
         if (device >= 0 && kv.first != device) continue;
         if (!kv.second) continue;
         std::lock_guard<std::mutex> lp(kv.second->mu);   // (no extract call in flight)

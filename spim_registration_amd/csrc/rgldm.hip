@@ -19,36 +19,27 @@
 //     division per descriptor pair
 //   * a descriptor pair whose min sum exceeds the sum behind the current second best cannot
 //     pass "difference < secondBest" (monotone again) and skips that division
-//   k_rgldm_knn     per point the nn+re nearest others (brute force over LDS tiles, top-k in
-//                   registers, ties by lower index), neighbour - basis in double
+//   k_pm_knn        (pointmatch.hip) per point the nn+re nearest others, neighbour - basis in double
 //   k_rgldm_match   a lane owns one A descriptor in registers; B descriptors go through LDS in
 //                   tiles and are read as broadcasts; grid.y splits B (partial best / second)
 //   k_rgldm_merge   partials -> best by (value, index), second = 2nd smallest of the four
-//   k_rgldm_compact the candidates in ascending A order (one block, chunked prefix sum)
+//   k_pm_compact    (pointmatch.hip) the candidates in ascending A order
+// The call around them -- argument rules, staging, "not enough detections", the result copies --
+// is pm_match_candidates (pointmatch.hpp), shared with geohash.hip.
 // No atomics; every output is written with ordinary stores.
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
-#include <map>
-#include <memory>
-#include <mutex>
 
-#include "common.hpp"
-#include "rgldm.hpp"
+#include "pointmatch.hpp"
 
 namespace spimdecon {
-
-bool is_device_ptr(const void* p, int dev);   // dog.hip
-
 namespace {
 
 constexpr int kRgATile = 128;    // A descriptors (lanes) per block of k_rgldm_match
 constexpr int kRgBTile = 64;     // B descriptors per LDS tile
-constexpr int kRgKnnBlock = 256;
 constexpr int kRgMaxM = 6;       // num_neighbors + redundancy
 constexpr int kRgMaxComb = 20;   // C(6, 3)
-constexpr int kRgScanBlock = 1024;
-constexpr double kJavaDoubleMax = DBL_MAX;   // Double.MAX_VALUE
 
 // SubsetMatcher.computePD(M, NN, 0) (:79-107): the NN-subsets of 0..M-1 in lexicographic order
 template <int NN>
@@ -73,84 +64,6 @@ constexpr RgComb<NN> rg_comb() {
     }
     t.n = n;
     return t;
-}
-
-// flag[0] = 1 when a coordinate is not finite as double or as float (Detection.get rounds to float)
-__global__ __launch_bounds__(256) void k_rgldm_finite(const double* __restrict__ p, int64_t n3,
-                                                      int* __restrict__ flag) {
-    int bad = 0;
-    for (int64_t i = int64_t(blockIdx.x) * 256 + threadIdx.x; i < n3; i += int64_t(gridDim.x) * 256) {
-        const float f = float(p[i]);
-        bad |= (f - f == 0.0f) ? 0 : 1;
-    }
-    if (bad) flag[0] = 1;   // (every writer stores the same value)
-}
-
-// Detection.distanceTo's argument: per-axis float differences, squared and summed in double
-__device__ __forceinline__ double rg_knn_s(float ax, float ay, float az, float bx, float by, float bz) {
-    const double x = double(__fsub_rn(bx, ax)), y = double(__fsub_rn(by, ay)), z = double(__fsub_rn(bz, az));
-    return __dadd_rn(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)), __dmul_rn(z, z));
-}
-
-template <int M>
-__global__ __launch_bounds__(kRgKnnBlock) void k_rgldm_knn(const double* __restrict__ pts, int n,
-                                                           int* __restrict__ neighbors,
-                                                           double* __restrict__ rel) {
-    __shared__ float tile[kRgKnnBlock * 3];
-    const int i = int(blockIdx.x) * kRgKnnBlock + int(threadIdx.x);
-    const int ic = min(i, n - 1);
-    const float ax = float(pts[3 * int64_t(ic)]), ay = float(pts[3 * int64_t(ic) + 1]),
-                az = float(pts[3 * int64_t(ic) + 2]);
-    float dist[M];   // ascending; (float) Math.sqrt(...) as the kd-tree compares it
-    int idx[M];
-#pragma unroll
-    for (int k = 0; k < M; ++k) {
-        dist[k] = __builtin_inff();
-        idx[k] = -1;
-    }
-    double s_worst = __builtin_inf();   // the double sum behind dist[M - 1]
-    for (int j0 = 0; j0 < n; j0 += kRgKnnBlock) {
-        const int cnt = min(kRgKnnBlock, n - j0);
-        __syncthreads();
-        for (int e = int(threadIdx.x); e < cnt * 3; e += kRgKnnBlock) tile[e] = float(pts[3 * int64_t(j0) + e]);
-        __syncthreads();
-        for (int t = 0; t < cnt; ++t) {
-            const int j = j0 + t;
-            const double s = rg_knn_s(ax, ay, az, tile[3 * t], tile[3 * t + 1], tile[3 * t + 2]);
-            // s > s_worst: the rounded root is no smaller than the worst kept (monotone): not "<"
-            if (j == ic || !(s <= s_worst)) continue;
-            const float d = float(__dsqrt_rn(s));
-            if (!(d < dist[M - 1])) continue;
-            dist[M - 1] = d;
-            idx[M - 1] = j;
-#pragma unroll
-            for (int k = M - 1; k > 0; --k) {   // strict <: an equal distance stays behind the lower index
-                if (dist[k] < dist[k - 1]) {
-                    const float td = dist[k]; dist[k] = dist[k - 1]; dist[k - 1] = td;
-                    const int ti = idx[k]; idx[k] = idx[k - 1]; idx[k - 1] = ti;
-                }
-            }
-            if (idx[M - 1] >= 0) {
-                // the sum of the worst kept is not tracked through the swaps: rebuild it
-                const int w = idx[M - 1];
-                s_worst = rg_knn_s(ax, ay, az, float(pts[3 * int64_t(w)]), float(pts[3 * int64_t(w) + 1]),
-                                   float(pts[3 * int64_t(w) + 2]));
-            }
-        }
-    }
-    if (i >= n) return;
-#pragma unroll
-    for (int k = 0; k < M; ++k) {
-        const int64_t o = int64_t(i) * M + k;
-        const int w = idx[k];
-        neighbors[o] = w;
-        const int wc = w < 0 ? i : w;   // (fewer than M finite distances: no neighbour, NaN)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const double v = __dsub_rn(pts[3 * int64_t(wc) + c], pts[3 * int64_t(i) + c]);
-            rel[o * 3 + c] = w < 0 ? __builtin_nan("") : v;
-        }
-    }
 }
 
 // One block: kRgATile A descriptors against the B descriptors of partition blockIdx.y.
@@ -254,73 +167,11 @@ __global__ __launch_bounds__(256) void k_rgldm_merge(int na, int nparts, const d
     flag[i] = (best < thr && __dmul_rn(best, ratio) < second) ? 1 : 0;
 }
 
-// One block: thread t owns the chunk [t * per, (t + 1) * per) of A; an exclusive scan of the
-// chunk counts gives each chunk's first output slot.  count[0] = all candidates (may exceed cap).
-__global__ __launch_bounds__(kRgScanBlock) void k_rgldm_compact(int na, const unsigned char* __restrict__ flag,
-                                                                const int* __restrict__ idx, int* __restrict__ cand_a,
-                                                                int* __restrict__ cand_b, int64_t cap,
-                                                                int64_t* __restrict__ count) {
-    __shared__ int sums[kRgScanBlock];
-    const int t = int(threadIdx.x);
-    const int per = (na + kRgScanBlock - 1) / kRgScanBlock;
-    const int64_t lo = int64_t(t) * per, hi = min(lo + per, int64_t(na));
-    int c = 0;
-    for (int64_t i = lo; i < hi; ++i) c += flag[i];
-    sums[t] = c;
-    __syncthreads();
-    for (int o = 1; o < kRgScanBlock; o <<= 1) {   // inclusive scan
-        const int v = t >= o ? sums[t - o] : 0;
-        __syncthreads();
-        sums[t] += v;
-        __syncthreads();
-    }
-    int64_t pos = sums[t] - c;
-    for (int64_t i = lo; i < hi; ++i) {
-        if (!flag[i]) continue;
-        if (pos < cap) {
-            cand_a[pos] = int(i);
-            cand_b[pos] = idx[i];
-        }
-        ++pos;
-    }
-    if (t == kRgScanBlock - 1) count[0] = sums[t];
-}
-
-__global__ __launch_bounds__(256) void k_rgldm_fill(int na, double* __restrict__ best, double* __restrict__ second,
-                                                    int* __restrict__ idx) {
-    const int i = int(blockIdx.x) * 256 + int(threadIdx.x);
-    if (i >= na) return;
-    best[i] = kJavaDoubleMax;
-    second[i] = kJavaDoubleMax;
-    idx[i] = -1;
-}
-
-// Per-device workspace, grown on demand and kept between calls (never destroyed: no hipFree
-// from a static destructor racing the runtime's teardown).
-struct RgWork {
-    std::mutex mu;
-    hipStream_t stream = nullptr;
-    DBuf<double> pts_a, pts_b, rel_a, rel_b, pbest, psecond, best, second;
-    DBuf<int> nbr_a, nbr_b, pidx, idx, cand_a, cand_b, bad;
-    DBuf<unsigned char> flag;
-    DBuf<int64_t> count;
-    hipStream_t get_stream() {
-        if (!stream) SD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        return stream;
-    }
+// Per-device workspace, grown on demand and kept between calls.
+struct RgWork : PmCandidateWork {
+    DBuf<double> rel_a, rel_b, pbest, psecond;
+    DBuf<int> nbr_a, nbr_b, pidx;
 };
-std::mutex g_rgwork_mu;
-std::map<int, std::unique_ptr<RgWork>>& g_rgwork = *new std::map<int, std::unique_ptr<RgWork>>();
-RgWork& rg_work(int dev) {
-    std::lock_guard<std::mutex> lk(g_rgwork_mu);
-    auto& w = g_rgwork[dev];
-    if (!w) w.reset(new RgWork());
-    return *w;
-}
-template <typename T>
-void rg_grow(DBuf<T>& b, size_t n) {
-    if (b.n < n) b.alloc(n);
-}
 
 // every argument rule that needs no GPU; returns nn + re
 int rg_check_params(const spim_rgldm_params* p) {
@@ -331,44 +182,6 @@ int rg_check_params(const spim_rgldm_params* p) {
              "rgldm: num_neighbors + redundancy beyond the supported maximum of 6");
     SD_CHECK(p->b_split >= 0, SPIMDECON_ERR_ARG, "rgldm: b_split must be >= 0");
     return p->num_neighbors + p->redundancy;
-}
-
-void rg_check_points(const double* pts, int64_t n) {
-    SD_CHECK(n >= 0 && (pts || n == 0), SPIMDECON_ERR_ARG, "null argument");
-    SD_CHECK(n <= int64_t(INT32_MAX), SPIMDECON_ERR_ARG, "rgldm: more than 2^31 - 1 points");
-}
-
-// the points on the device (in place when they already are) and checked finite
-const double* rg_stage(const double* pts, int64_t n, int dev, DBuf<double>& buf, DBuf<int>& bad_buf, hipStream_t s,
-                       const char* who = "rgldm") {
-    const double* d = pts;
-    if (!is_device_ptr(pts, dev)) {
-        rg_grow(buf, size_t(3 * n));
-        SD_HIP(hipMemcpyAsync(buf.p, pts, size_t(3 * n) * sizeof(double), hipMemcpyDefault, s));
-        d = buf.p;
-    }
-    rg_grow(bad_buf, 1);
-    SD_HIP(hipMemsetAsync(bad_buf.p, 0, sizeof(int), s));
-    const unsigned g = unsigned(std::min<int64_t>(ceil_div(3 * n, 256), 1024));
-    hipLaunchKernelGGL(k_rgldm_finite, dim3(g), dim3(256), 0, s, d, 3 * n, bad_buf.p);
-    SD_HIP(hipGetLastError());
-    int bad = 0;
-    SD_HIP(hipMemcpyAsync(&bad, bad_buf.p, sizeof(int), hipMemcpyDeviceToHost, s));
-    SD_HIP(hipStreamSynchronize(s));
-    SD_CHECK(!bad, SPIMDECON_ERR_ARG, std::string(who) + ": non-finite coordinates");
-    return d;
-}
-
-void rg_knn(const double* dpts, int n, int m, int* nbr, double* rel, hipStream_t s) {
-    const unsigned g = unsigned(ceil_div(n, kRgKnnBlock));
-#define SD_RG_KNN(MV) \
-    case MV: hipLaunchKernelGGL(k_rgldm_knn<MV>, dim3(g), dim3(kRgKnnBlock), 0, s, dpts, n, nbr, rel); break;
-    switch (m) {
-        SD_RG_KNN(1) SD_RG_KNN(2) SD_RG_KNN(3) SD_RG_KNN(4) SD_RG_KNN(5) SD_RG_KNN(6)
-        default: fail(SPIMDECON_ERR_ARG, "rgldm: unsupported neighbour count");
-    }
-#undef SD_RG_KNN
-    SD_HIP(hipGetLastError());
 }
 
 void rg_match_launch(int nn, int m, dim3 grid, hipStream_t s, const double* ra, int na, const double* rb, int nb,
@@ -389,18 +202,18 @@ void rg_match_launch(int nn, int m, dim3 grid, hipStream_t s, const double* ra, 
 
 void rgldm_descriptors(const double* pts, int64_t n, const spim_rgldm_params* p, int32_t* neighbors, double* rel) {
     const int m = rg_check_params(p);
-    rg_check_points(pts, n);
+    pm_check_points(pts, n, "rgldm");
     SD_CHECK(neighbors && rel, SPIMDECON_ERR_ARG, "null argument");
     SD_CHECK(n >= m + 1, SPIMDECON_ERR_ARG, "rgldm: a descriptor needs num_neighbors + redundancy + 1 points");
     check_device(p->device);
     DeviceGuard guard(p->device);
-    RgWork& w = rg_work(p->device);
+    RgWork& w = per_device<RgWork>(p->device);
     std::lock_guard<std::mutex> lk(w.mu);
     hipStream_t s = w.get_stream();
-    const double* d = rg_stage(pts, n, p->device, w.pts_a, w.bad, s);
-    rg_grow(w.nbr_a, size_t(n) * m);
-    rg_grow(w.rel_a, size_t(n) * m * 3);
-    rg_knn(d, int(n), m, w.nbr_a.p, w.rel_a.p, s);
+    const double* d = pm_stage_points(pts, n, p->device, w.pts_a, w.bad, s, "rgldm");
+    grow(w.nbr_a, size_t(n) * m);
+    grow(w.rel_a, size_t(n) * m * 3);
+    pm_knn(d, int(n), m, w.nbr_a.p, w.rel_a.p, s);
     SD_HIP(hipMemcpyAsync(neighbors, w.nbr_a.p, size_t(n) * m * sizeof(int), hipMemcpyDefault, s));
     SD_HIP(hipMemcpyAsync(rel, w.rel_a.p, size_t(n) * m * 3 * sizeof(double), hipMemcpyDefault, s));
     SD_HIP(hipStreamSynchronize(s));
@@ -410,98 +223,34 @@ void rgldm_match(const double* a, int64_t na, const double* b, int64_t nb, const
                  int32_t* best_idx, double* best, double* second, int32_t* cand_a, int32_t* cand_b, int64_t cap,
                  int64_t* count) {
     const int m = rg_check_params(p);
-    rg_check_points(a, na);
-    rg_check_points(b, nb);
-    SD_CHECK(count && cap >= 0 && (cap == 0 || (cand_a && cand_b)), SPIMDECON_ERR_ARG, "null argument");
-    SD_CHECK(na == 0 || (best_idx && best && second), SPIMDECON_ERR_ARG, "null argument");
-    *count = 0;
-    check_device(p->device);
-    DeviceGuard guard(p->device);
-    RgWork& w = rg_work(p->device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    hipStream_t s = w.get_stream();
-    const double* da = na ? rg_stage(a, na, p->device, w.pts_a, w.bad, s) : nullptr;
-    const double* db = nb ? rg_stage(b, nb, p->device, w.pts_b, w.bad, s) : nullptr;
-    if (na == 0) return;
-    rg_grow(w.best, size_t(na));
-    rg_grow(w.second, size_t(na));
-    rg_grow(w.idx, size_t(na));
-    const unsigned ga = unsigned(ceil_div(na, 256));
-    if (na < m + 1 || nb < m + 1) {
-        // RGLDMPairwise.java:46-54, "Not enough detections to match": no candidates
-        hipLaunchKernelGGL(k_rgldm_fill, dim3(ga), dim3(256), 0, s, int(na), w.best.p, w.second.p, w.idx.p);
-        SD_HIP(hipGetLastError());
-    } else {
-        rg_grow(w.nbr_a, size_t(na) * m);
-        rg_grow(w.rel_a, size_t(na) * m * 3);
-        rg_grow(w.nbr_b, size_t(nb) * m);
-        rg_grow(w.rel_b, size_t(nb) * m * 3);
-        rg_knn(da, int(na), m, w.nbr_a.p, w.rel_a.p, s);
-        rg_knn(db, int(nb), m, w.nbr_b.p, w.rel_b.p, s);
-        // B split: 313 wavefronts of A (20,000 beads) do not fill the device; aim at ~8 waves per CU
-        const int64_t ablocks = ceil_div(na, kRgATile);
-        int64_t split = p->b_split;
-        if (split <= 0) {
-            int cus = 0;
-            SD_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device));
-            const int64_t want = int64_t(cus) * 4;   // blocks of 2 waves
-            split = std::min<int64_t>(std::max<int64_t>(ceil_div(want, ablocks), 1), ceil_div(nb, kRgBTile));
-        }
-        split = std::min<int64_t>(split, 65535);
-        const int chunk = int(ceil_div(nb, split));
-        SD_CHECK(ablocks * split < (int64_t(1) << 31), SPIMDECON_ERR_ARG, "rgldm: too many blocks");
-        rg_grow(w.pbest, size_t(na) * split);
-        rg_grow(w.psecond, size_t(na) * split);
-        rg_grow(w.pidx, size_t(na) * split);
-        rg_match_launch(p->num_neighbors, m, dim3(unsigned(ablocks), unsigned(split)), s, w.rel_a.p, int(na),
-                        w.rel_b.p, int(nb), chunk, w.pbest.p, w.psecond.p, w.pidx.p);
-        SD_HIP(hipGetLastError());
-        rg_grow(w.flag, size_t(na));
-        hipLaunchKernelGGL(k_rgldm_merge, dim3(ga), dim3(256), 0, s, int(na), int(split), w.pbest.p, w.psecond.p,
-                           w.pidx.p, double(p->difference_threshold), double(p->ratio_of_distance), w.best.p,
-                           w.second.p, w.idx.p, w.flag.p);
-        SD_HIP(hipGetLastError());
-        rg_grow(w.count, 1);
-        const int64_t dcap = std::min<int64_t>(cap, na);
-        rg_grow(w.cand_a, size_t(std::max<int64_t>(dcap, 1)));
-        rg_grow(w.cand_b, size_t(std::max<int64_t>(dcap, 1)));
-        hipLaunchKernelGGL(k_rgldm_compact, dim3(1), dim3(kRgScanBlock), 0, s, int(na), w.flag.p, w.idx.p,
-                           w.cand_a.p, w.cand_b.p, dcap, w.count.p);
-        SD_HIP(hipGetLastError());
-        SD_HIP(hipMemcpyAsync(count, w.count.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    }
-    SD_HIP(hipMemcpyAsync(best_idx, w.idx.p, size_t(na) * sizeof(int), hipMemcpyDefault, s));
-    SD_HIP(hipMemcpyAsync(best, w.best.p, size_t(na) * sizeof(double), hipMemcpyDefault, s));
-    SD_HIP(hipMemcpyAsync(second, w.second.p, size_t(na) * sizeof(double), hipMemcpyDefault, s));
-    SD_HIP(hipStreamSynchronize(s));
-    SD_CHECK(*count <= cap, SPIMDECON_ERR_ARG,
-             "rgldm: " + std::to_string(*count) + " candidates beyond the capacity " + std::to_string(cap));
-    if (*count) {
-        SD_HIP(hipMemcpyAsync(cand_a, w.cand_a.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
-        SD_HIP(hipMemcpyAsync(cand_b, w.cand_b.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
-        SD_HIP(hipStreamSynchronize(s));
-    }
+    // fewer than m + 1 points: RGLDMPairwise.java:46-54, "Not enough detections to match": no candidates
+    pm_match_candidates<RgWork>(
+        "rgldm", m + 1, p->device, a, na, b, nb, best_idx, best, second, cand_a, cand_b, cap, count,
+        [&](RgWork& w, const double* da, const double* db, hipStream_t s) {
+            grow(w.nbr_a, size_t(na) * m);
+            grow(w.rel_a, size_t(na) * m * 3);
+            grow(w.nbr_b, size_t(nb) * m);
+            grow(w.rel_b, size_t(nb) * m * 3);
+            pm_knn(da, int(na), m, w.nbr_a.p, w.rel_a.p, s);
+            pm_knn(db, int(nb), m, w.nbr_b.p, w.rel_b.p, s);
+            // B split: 313 wavefronts of A (20,000 beads) do not fill the device; aim at ~8 waves per CU
+            const int64_t ablocks = ceil_div(na, kRgATile);
+            const PmSplit sp = pm_split(p->b_split, ablocks, nb, kRgBTile, 4 /* blocks of 2 waves */, p->device,
+                                        "rgldm");
+            grow(w.pbest, size_t(na) * sp.split);
+            grow(w.psecond, size_t(na) * sp.split);
+            grow(w.pidx, size_t(na) * sp.split);
+            rg_match_launch(p->num_neighbors, m, dim3(unsigned(ablocks), unsigned(sp.split)), s, w.rel_a.p, int(na),
+                            w.rel_b.p, int(nb), sp.chunk, w.pbest.p, w.psecond.p, w.pidx.p);
+            SD_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_rgldm_merge, dim3(unsigned(ceil_div(na, 256))), dim3(256), 0, s, int(na),
+                               int(sp.split), w.pbest.p, w.psecond.p, w.pidx.p, double(p->difference_threshold),
+                               double(p->ratio_of_distance), w.best.p, w.second.p, w.idx.p, w.flag.p);
+            SD_HIP(hipGetLastError());
+        });
 }
 
 }  // namespace
-
-// ---------------------------------------------------------------- shared with geohash.hip (rgldm.hpp)
-const double* pm_stage_points(const double* pts, int64_t n, int dev, DBuf<double>& buf, DBuf<int>& bad,
-                              hipStream_t s, const char* who) {
-    rg_check_points(pts, n);
-    return rg_stage(pts, n, dev, buf, bad, s, who);
-}
-
-void pm_knn(const double* dpts, int n, int m, int* nbr, double* rel, hipStream_t s) {
-    rg_knn(dpts, n, m, nbr, rel, s);
-}
-
-void pm_compact(int na, const unsigned char* flag, const int* idx, int* cand_a, int* cand_b, int64_t cap,
-                int64_t* count, hipStream_t s) {
-    hipLaunchKernelGGL(k_rgldm_compact, dim3(1), dim3(kRgScanBlock), 0, s, na, flag, idx, cand_a, cand_b, cap, count);
-    SD_HIP(hipGetLastError());
-}
-
 }  // namespace spimdecon
 
 // ---------------------------------------------------------------- extern "C"

@@ -61,6 +61,7 @@ kd-tree is not in its tree) and mpicbg's ``fit`` / ``apply`` (restated in ``glob
 from __future__ import annotations
 
 import ctypes as C
+import functools
 
 import numpy as np
 
@@ -97,11 +98,28 @@ def _points(x):
     return C.c_void_p(a.ctypes.data), len(a), a
 
 
+def _tiles(fn):
+    a, b = C.c_int32(0), C.c_int32(0)
+    fn(C.byref(a), C.byref(b))
+    return int(a.value), int(b.value)
+
+
+def _candidates(fn, params, pa, pb, return_all):
+    """a candidate matcher's call (``spim_rgldm_match`` / ``spim_gh_match``) and its results"""
+    aptr, na, _ka = _points(pa)
+    bptr, nb, _kb = _points(pb)
+    idx, best, second = np.empty(na, np.int32), np.empty(na, np.float64), np.empty(na, np.float64)
+    ia, ib = np.empty(max(na, 1), np.int32), np.empty(max(na, 1), np.int32)   # at most one candidate per A point
+    n = C.c_int64(0)
+    check(fn(aptr, na, bptr, nb, C.byref(params), C.c_void_p(idx.ctypes.data), C.c_void_p(best.ctypes.data),
+             C.c_void_p(second.ctypes.data), C.c_void_p(ia.ctypes.data), C.c_void_p(ib.ctypes.data), na, C.byref(n)))
+    ia, ib = ia[:n.value].copy(), ib[:n.value].copy()
+    return (ia, ib, idx, best, second) if return_all else (ia, ib)
+
+
 def tile_sizes():
     """(A descriptors per block, B descriptors per LDS tile) of the matching kernel."""
-    a, b = C.c_int32(0), C.c_int32(0)
-    _lib.load().spim_rgldm_tiles(C.byref(a), C.byref(b))
-    return int(a.value), int(b.value)
+    return _tiles(_lib.load().spim_rgldm_tiles)
 
 
 def descriptors(points, num_neighbors: int = 3, redundancy: int = 1, device: int = 0):
@@ -127,16 +145,7 @@ def rgldm_candidates(pa, pb, num_neighbors: int = 3, redundancy: int = 1, ratio_
     result does not depend on it)."""
     lib = _lib.load()
     p = _params(lib, num_neighbors, redundancy, ratio_of_distance, difference_threshold, device, b_split)
-    aptr, na, _ka = _points(pa)
-    bptr, nb, _kb = _points(pb)
-    idx, best, second = np.empty(na, np.int32), np.empty(na, np.float64), np.empty(na, np.float64)
-    ia, ib = np.empty(max(na, 1), np.int32), np.empty(max(na, 1), np.int32)   # at most one candidate per A point
-    n = C.c_int64(0)
-    check(lib.spim_rgldm_match(aptr, na, bptr, nb, C.byref(p), C.c_void_p(idx.ctypes.data),
-                               C.c_void_p(best.ctypes.data), C.c_void_p(second.ctypes.data),
-                               C.c_void_p(ia.ctypes.data), C.c_void_p(ib.ctypes.data), na, C.byref(n)))
-    ia, ib = ia[:n.value].copy(), ib[:n.value].copy()
-    return (ia, ib, idx, best, second) if return_all else (ia, ib)
+    return _candidates(lib.spim_rgldm_match, p, pa, pb, return_all)
 
 
 def _gh_params(lib, ratio_of_distance, difference_threshold, device, b_split=0):
@@ -150,9 +159,7 @@ def _gh_params(lib, ratio_of_distance, difference_threshold, device, b_split=0):
 def gh_tile_sizes():
     """(A descriptors per block, B descriptors per LDS tile) of the geometric hashing
     matching kernel."""
-    a, b = C.c_int32(0), C.c_int32(0)
-    _lib.load().spim_gh_tiles(C.byref(a), C.byref(b))
-    return int(a.value), int(b.value)
+    return _tiles(_lib.load().spim_gh_tiles)
 
 
 def gh_descriptors(points, device: int = 0):
@@ -177,23 +184,12 @@ def gh_candidates(pa, pb, ratio_of_distance: float = 10.0, difference_threshold:
     ``b_split`` forces the partitions of B (0 = auto; the result does not depend on it)."""
     lib = _lib.load()
     p = _gh_params(lib, ratio_of_distance, difference_threshold, device, b_split)
-    aptr, na, _ka = _points(pa)
-    bptr, nb, _kb = _points(pb)
-    idx, best, second = np.empty(na, np.int32), np.empty(na, np.float64), np.empty(na, np.float64)
-    ia, ib = np.empty(max(na, 1), np.int32), np.empty(max(na, 1), np.int32)   # at most one candidate per A point
-    n = C.c_int64(0)
-    check(lib.spim_gh_match(aptr, na, bptr, nb, C.byref(p), C.c_void_p(idx.ctypes.data),
-                            C.c_void_p(best.ctypes.data), C.c_void_p(second.ctypes.data),
-                            C.c_void_p(ia.ctypes.data), C.c_void_p(ib.ctypes.data), na, C.byref(n)))
-    ia, ib = ia[:n.value].copy(), ib[:n.value].copy()
-    return (ia, ib, idx, best, second) if return_all else (ia, ib)
+    return _candidates(lib.spim_gh_match, p, pa, pb, return_all)
 
 
 def icp_tile_sizes():
     """(reference points per block, target points per LDS tile) of the ICP assignment kernel."""
-    a, b = C.c_int32(0), C.c_int32(0)
-    _lib.load().spim_icp_tiles(C.byref(a), C.byref(b))
-    return int(a.value), int(b.value)
+    return _tiles(_lib.load().spim_icp_tiles)
 
 
 def icp_assign(target, reference, model=None, max_distance: float = 5.0, device: int = 0, return_all: bool = False,
@@ -272,6 +268,25 @@ def icp(pa, pb, model: str = "affine", max_distance: float = 5.0, max_iterations
     return it, ir, m, err, i
 
 
+def _world_and_pairs(points, models, pairs):
+    """(the views' detections mapped by their current models, the given pairs or all of them)"""
+    world = [globalopt.apply(np.asarray(m, np.float64).reshape(3, 4), np.asarray(p, np.float64).reshape(-1, 3))
+             for p, m in zip(points, models)]
+    if pairs is None:
+        pairs = [(a, b) for a in range(len(world)) for b in range(a + 1, len(world))]
+    return world, pairs
+
+
+def _refine(models, matches, model, fixed):
+    """``globalopt.compute`` over the pairwise matches and ``globalopt.concatenate`` onto the
+    given 3x4 models: (the refined models -- the given ones when no pair has matches --, the
+    GlobalOptResult or None)"""
+    res = globalopt.compute(len(models), matches, model=model, fixed=fixed)
+    if res is not None:
+        models = [globalopt.concatenate(c, m) for c, m in zip(res.models, models)]
+    return models, res
+
+
 def pairwise_icp(points, models, pairs=None, model: str = "affine", max_distance: float = 5.0,
                  max_iterations: int = 100, device: int = 0, assign=None):
     """IterativeClosestPointPairwise.call over all view pairs (or ``pairs``, (a, b) tuples): the
@@ -279,10 +294,7 @@ def pairwise_icp(points, models, pairs=None, model: str = "affine", max_distance
     reference of ``icp``.  Returns the pairs with matches as ``globalopt.PairwiseMatch`` over
     world points under ``models`` (the last iteration's matches are candidates and inliers
     alike; the pair's model is not passed on, the global optimisation refits)."""
-    world = [globalopt.apply(np.asarray(m, np.float64).reshape(3, 4), np.asarray(p, np.float64).reshape(-1, 3))
-             for p, m in zip(points, models)]
-    if pairs is None:
-        pairs = [(a, b) for a in range(len(world)) for b in range(a + 1, len(world))]
+    world, pairs = _world_and_pairs(points, models, pairs)
     out = []
     for a, b in pairs:
         it, ir, _, _, _ = icp(world[a], world[b], model, max_distance, max_iterations, device, assign)
@@ -297,11 +309,7 @@ def register_icp(points, models, model: str = "affine", fixed=(0,), **kw):
     keywords pass through), ``globalopt.compute`` and ``globalopt.concatenate``.  Returns what
     ``register`` returns."""
     models = [np.asarray(m, np.float64).reshape(3, 4) for m in models]
-    matches = pairwise_icp(points, models, model=model, **kw)
-    res = globalopt.compute(len(models), matches, model=model, fixed=fixed)
-    if res is not None:
-        models = [globalopt.concatenate(c, m) for c, m in zip(res.models, models)]
-    return models, res
+    return _refine(models, pairwise_icp(points, models, model=model, **kw), model, fixed)
 
 
 def _inliers(kind, pa, pb, sel, eps):
@@ -368,6 +376,20 @@ def ransac(pa, pb, model: str = "affine", max_epsilon: float = 5.0, min_inlier_r
     return inl, m, cost
 
 
+def _pairwise_ransac(world, pairs, find, model, max_epsilon, min_inlier_ratio, min_inlier_factor, num_iterations,
+                     seed):
+    """per pair the candidates ``find(pa, pb) -> (ia, ib)`` through ``ransac``: the pairs with
+    inliers as ``globalopt.PairwiseMatch``"""
+    out = []
+    for a, b in pairs:
+        ia, ib = find(world[a], world[b])
+        ca, cb = world[a][ia], world[b][ib]
+        inl, _, _ = ransac(ca, cb, model, max_epsilon, min_inlier_ratio, min_inlier_factor, num_iterations, seed)
+        if len(inl):
+            out.append(globalopt.PairwiseMatch(a, b, ca[inl], cb[inl]))
+    return out
+
+
 def pairwise_rgldm(points, models, pairs=None, model: str = "affine", num_neighbors: int = 3, redundancy: int = 1,
                    ratio_of_distance: float = 3.0, difference_threshold: float = 50.0, max_epsilon: float = 5.0,
                    min_inlier_ratio: float = 0.1, min_inlier_factor: float = 3.0, num_iterations: int = 1000,
@@ -378,23 +400,13 @@ def pairwise_rgldm(points, models, pairs=None, model: str = "affine", num_neighb
     as ``globalopt.PairwiseMatch`` over world points under ``models``.  ``candidates``: a
     callable (pa, pb, **rgldm parameters) -> (ia, ib) to use in place of the GPU matcher
     (the tests feed the restatement's candidates through the same code)."""
-    world = [globalopt.apply(np.asarray(m, np.float64).reshape(3, 4), np.asarray(p, np.float64).reshape(-1, 3))
-             for p, m in zip(points, models)]
-    if pairs is None:
-        pairs = [(a, b) for a in range(len(world)) for b in range(a + 1, len(world))]
+    world, pairs = _world_and_pairs(points, models, pairs)
     kw = dict(num_neighbors=num_neighbors, redundancy=redundancy, ratio_of_distance=ratio_of_distance,
               difference_threshold=difference_threshold)
-    out = []
-    for a, b in pairs:
-        if candidates is None:
-            ia, ib = rgldm_candidates(world[a], world[b], device=device, **kw)
-        else:
-            ia, ib = candidates(world[a], world[b], **kw)
-        ca, cb = world[a][ia], world[b][ib]
-        inl, _, _ = ransac(ca, cb, model, max_epsilon, min_inlier_ratio, min_inlier_factor, num_iterations, seed)
-        if len(inl):
-            out.append(globalopt.PairwiseMatch(a, b, ca[inl], cb[inl]))
-    return out
+    if candidates is None:
+        candidates = functools.partial(rgldm_candidates, device=device)
+    return _pairwise_ransac(world, pairs, functools.partial(candidates, **kw), model, max_epsilon, min_inlier_ratio,
+                            min_inlier_factor, num_iterations, seed)
 
 
 def pairwise_geometric_hashing(points, models, pairs=None, model: str = "affine", ratio_of_distance: float = 10.0,
@@ -407,22 +419,12 @@ def pairwise_geometric_hashing(points, models, pairs=None, model: str = "affine"
     (``gh_candidates``) in place of RGLDM's, so the ``models`` need not be rotationally
     right.  ``candidates``: a callable (pa, pb, ratio_of_distance=, difference_threshold=)
     -> (ia, ib) to use in place of the GPU matcher."""
-    world = [globalopt.apply(np.asarray(m, np.float64).reshape(3, 4), np.asarray(p, np.float64).reshape(-1, 3))
-             for p, m in zip(points, models)]
-    if pairs is None:
-        pairs = [(a, b) for a in range(len(world)) for b in range(a + 1, len(world))]
+    world, pairs = _world_and_pairs(points, models, pairs)
     kw = dict(ratio_of_distance=ratio_of_distance, difference_threshold=difference_threshold)
-    out = []
-    for a, b in pairs:
-        if candidates is None:
-            ia, ib = gh_candidates(world[a], world[b], device=device, **kw)
-        else:
-            ia, ib = candidates(world[a], world[b], **kw)
-        ca, cb = world[a][ia], world[b][ib]
-        inl, _, _ = ransac(ca, cb, model, max_epsilon, min_inlier_ratio, min_inlier_factor, num_iterations, seed)
-        if len(inl):
-            out.append(globalopt.PairwiseMatch(a, b, ca[inl], cb[inl]))
-    return out
+    if candidates is None:
+        candidates = functools.partial(gh_candidates, device=device)
+    return _pairwise_ransac(world, pairs, functools.partial(candidates, **kw), model, max_epsilon, min_inlier_ratio,
+                            min_inlier_factor, num_iterations, seed)
 
 
 def register(points, models, model: str = "affine", fixed=(0,), matching: str = "rgldm", **kw):
@@ -435,8 +437,4 @@ def register(points, models, model: str = "affine", fixed=(0,), matching: str = 
         raise ValueError(f"matching must be 'rgldm' or 'geometric_hashing', not {matching!r}")
     models = [np.asarray(m, np.float64).reshape(3, 4) for m in models]
     pairwise = pairwise_rgldm if matching == "rgldm" else pairwise_geometric_hashing
-    matches = pairwise(points, models, model=model, **kw)
-    res = globalopt.compute(len(models), matches, model=model, fixed=fixed)
-    if res is not None:
-        models = [globalopt.concatenate(c, m) for c, m in zip(res.models, models)]
-    return models, res
+    return _refine(models, pairwise(points, models, model=model, **kw), model, fixed)

@@ -32,7 +32,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 # profiles/gh_bench.json at 16,000: two spim_gh_descriptors calls (1.90 ms each), that is the
-# neighbour search k_rgldm_knn<3> of both lists -- 2 n^2 point pairs through the same
+# neighbour search k_pm_knn<3> of both lists -- 2 n^2 point pairs through the same
 # Detection.distanceTo chain -- with their finite checks, descriptors and copies out
 GH_KNN_MS_16000 = 3.8
 
