@@ -145,4 +145,9 @@ int guarded(F&& fn) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// the extents of a volume, x fastest (sepconv, the detectors)
+struct Dims3 {
+    int64_t nx, ny, nz;
+};
+
 }  // namespace spimdecon

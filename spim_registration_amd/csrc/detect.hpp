@@ -1,0 +1,191 @@
+// detect.hpp -- what the detectors (dog.hip, dom.hip) and the downsampler (downsample.hip)
+// share (detect.hip): the per-device workspace with its mutex and stream, the scaffold of a
+// call, and the detection stage -- everything that starts from a stored device image: the
+// candidate pass (InteractiveIntegral.findPeaks), the x % T order, the fit and the selection.
+#pragma once
+
+#include <algorithm>
+
+#include "common.hpp"
+
+namespace spimdecon {
+
+constexpr int kBlock = 256;
+inline unsigned grid_of(int64_t n, int64_t cap = 4096) {
+    int64_t b = ceil_div(n, kBlock);
+    return unsigned(b < 1 ? 1 : (b > cap ? cap : b));
+}
+
+// a float image of n voxels lies below 4 GiB: one buffer resource with 32-bit offsets covers
+// it (k_dog_peaks and the buffer loads of k_dog_xy address it so)
+inline bool image_below_4gib(int64_t n) { return uint64_t(n) * 4u < 0xffffffffull; }
+
+struct PeakOut {   // (cand_flush writes it as three int pairs)
+    int32_t x, y, z;
+    float intensity;
+    int32_t is_min, is_max;
+};
+
+// candidate sink: unordered append of (key, record); count may exceed cap (the host reruns)
+struct PeakSink {
+    float minv;
+    int want_min, want_max, T;
+    uint64_t* keys;
+    uint32_t* vals;
+    PeakOut* recs;
+    unsigned* count;
+    unsigned cap;
+};
+
+struct LocOut {
+    float pos[3];
+    float value;
+};
+
+// Per-device DoG workspace, grown on demand and kept between calls (a 768^3 view needs
+// ~3.6 GB of G12 plus the candidate lists; hipMalloc / hipFree of that per call cost
+// more than the DoG itself).  One call at a time per device holds its mutex;
+// spim_dog_release_workspace frees it.  (The DOM detector and the downsampler stage their
+// input in `in` and write their image to `dog`: they add no buffer of their own.)
+struct DogWork {
+    std::mutex mu;
+    DBuf<float> in, dog, taps, mm, tmp_a, tmp_b, tmp_c, tmp_d;
+    DBuf<float2> g12;
+    DBuf<uint64_t> keys, keys_sorted;
+    DBuf<uint32_t> vals, vals_sorted;
+    DBuf<PeakOut> recs, peaks;
+    DBuf<unsigned> count;
+    DBuf<unsigned char> sort_tmp;
+    DBuf<LocOut> loc;                      // localisation results
+    DBuf<spim_interest_point> ips, ips_sel;  // interest points before / after the threshold
+    DBuf<unsigned char> flags, sel_tmp;
+    DBuf<int> nsel;
+    DBuf<PeakSink> sink;                   // the candidate kernels' sink, read at their flushes
+    // the calls' stream, created once (a stream per call cost ~1 ms of host time per
+    // 768^3 call: r3l trace, 1.17 ms before the first copy)
+    hipStream_t stream = nullptr;
+    hipStream_t get_stream() {
+        if (!stream) SD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        return stream;
+    }
+    void release() {
+        if (stream) {
+            (void)hipStreamDestroy(stream);
+            stream = nullptr;
+        }
+        auto all = [](auto&... b) { (b.release(), ...); };
+        all(in, dog, taps, mm, tmp_a, tmp_b, tmp_c, tmp_d, g12, keys, keys_sorted, vals, vals_sorted, recs, peaks, count,
+            sort_tmp, loc, ips, ips_sel, flags, sel_tmp, nsel, sink);
+    }
+};
+
+DogWork& dog_work(int dev);
+
+// ---------------------------------------------------------------- the call scaffold
+// body(w) on `device`, holding its workspace's mutex
+template <typename Body>
+void with_workspace(int device, Body&& body) {
+    check_device(device);
+    DeviceGuard guard(device);
+    DogWork& w = dog_work(device);
+    std::lock_guard<std::mutex> lk(w.mu);
+    body(w);
+}
+
+// One detector call: body(w, s) with the workspace's stream (held under its mutex)
+template <typename Body>
+void with_detector(int device, Body&& body) {
+    with_workspace(device, [&](DogWork& w) { body(w, w.get_stream()); });
+}
+
+// The argument rules DoG and DoM share; `own()` runs the detector's own between the view's
+// and the localisation's.
+template <typename Params, typename Own>
+void check_detector_args(const float* img, const int64_t* dims, const Params* p, Own&& own) {
+    SD_CHECK(img && dims && p, SPIMDECON_ERR_ARG, "null argument");
+    SD_CHECK(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, SPIMDECON_ERR_ARG, "bad dims");
+    own();
+    SD_CHECK(p->localization == 0 || p->localization == 1, SPIMDECON_ERR_ARG,
+             "localization must be 0 (none) or 1 (quadratic); the Gaussian fit is not implemented in "
+             "the reference either (Localization.java:90-96)");
+    SD_CHECK(p->ij_threads >= 1 && p->ij_threads < (1 << 20), SPIMDECON_ERR_ARG, "ij_threads must be >= 1");
+}
+
+// the view of n voxels: read in place when it already lives in the device's HBM, else one
+// upload into w.in (from the host or another device)
+const float* stage_view(DogWork& w, const float* img, int64_t n, int device, hipStream_t s);
+
+// Where a call's image of n voxels goes: the caller's buffer when that is memory of the
+// device, else the workspace's w.dog, copied out to the caller's (if any) at the end.
+struct ImageDest {
+    float* out;            // the caller's buffer, or nullptr
+    bool out_dev;          // ... is device memory
+    int64_t n;
+    float* p = nullptr;    // where the kernels write; nullptr: the image is not stored
+    ImageDest(float* out, int64_t n, int device) : out(out), out_dev(out && is_device_ptr(out, device)), n(n) {}
+    float* store(DogWork& w) {
+        if (!p && !out_dev) grow(w.dog, size_t(n));
+        if (!p) p = out_dev ? out : w.dog.p;
+        return p;
+    }
+    void copy_out(hipStream_t s) const {
+        if (out && !out_dev) SD_HIP(hipMemcpyAsync(out, p, n * 4, hipMemcpyDefault, s));
+    }
+};
+
+// ---------------------------------------------------------------- the detection stage
+// the detector's image (on the device) and the reference-ordered candidate list (on the device)
+struct DogRun {
+    Dims3 d{};
+    const float* dog = nullptr;   // nullptr when neither localisation nor the image was asked for
+    int64_t np = 0;
+    const PeakOut* dpeaks = nullptr;
+};
+
+// The candidate pass of a detector: `launch(pk, attempt)` enqueues the kernel(s) that append
+// to the sink pk; a count beyond the capacity reruns it once with room for every candidate.
+template <typename Launch>
+unsigned collect_candidates(DogWork& w, int64_t n, float min_peak, int wmin, int wmax, int T, hipStream_t s,
+                            Launch&& launch) {
+    grow(w.count, 1);
+    unsigned cap = unsigned(std::min<int64_t>(std::max<int64_t>(int64_t(1) << 16, n / 256), int64_t(1) << 30));
+    cap = std::max<unsigned>(cap, unsigned(std::min<size_t>(w.recs.n, size_t(1) << 30)));
+    unsigned total = 0;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        grow(w.keys, cap);
+        grow(w.vals, cap);
+        grow(w.recs, cap);
+        SD_HIP(hipMemsetAsync(w.count.p, 0, sizeof(unsigned), s));
+        const PeakSink pk{min_peak, wmin, wmax, T, w.keys.p, w.vals.p, w.recs.p, w.count.p, cap};
+        launch(pk, attempt);
+        SD_HIP(hipGetLastError());
+        SD_HIP(hipMemcpyAsync(&total, w.count.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        SD_HIP(hipStreamSynchronize(s));
+        if (total <= cap) break;
+        cap = total;          // rerun with room for every candidate (the image is already stored)
+    }
+    return total;
+}
+
+// candidates of a stored image: k_dog_peaks, or k_peaks_append where its limits are not met
+void stored_candidates(DogWork& w, const Dims3& d, const float* dogp, bool peaks_kernel, const PeakSink& pk,
+                       hipStream_t s);
+
+// reference order: ascending (x % T) << 40 | flat, into r.np / r.dpeaks
+void sort_candidates(DogWork& w, unsigned total, int T, hipStream_t s, DogRun& r);
+
+// InteractiveIntegral.findPeaks over a stored device image: the extrema with
+// |v| >= min_peak of the wanted kinds, in the reference's order, into r.np / r.dpeaks
+// (the workspace's memory).  Synchronises the stream.
+void detect_stored(DogWork& w, const Dims3& d, const float* img, float min_peak, int want_min, int want_max, int T,
+                   hipStream_t s, DogRun& r);
+
+// the first min(r.np, max_peaks) candidates to the host; *npeaks = r.np
+void peaks_to_host(const DogRun& r, spim_peak* peaks, int64_t max_peaks, int64_t* npeaks, hipStream_t s);
+
+// Localization.noLocalization (0) or computeQuadraticLocalization (1: the fit over r.dog,
+// kept when |fitted value| > keep_thr) of the candidates; out may be host or device memory
+void points_from_peaks(DogWork& w, const DogRun& r, int localization, float keep_thr, spim_interest_point* out,
+                       int64_t max_out, int64_t* nout, hipStream_t s);
+
+}  // namespace spimdecon

@@ -17,13 +17,13 @@
 //                of those go through two LDS tiles, then the two divisions and the store
 //   k_dom_frame  the zero frame (ProcessDOM.java:89-94: every voxel the boxes do not reach)
 // All sums are 64-bit (unsigned in the code: wrap-around is then defined).  Everything from
-// the stored image on is the detection stage of dog.hip (dog_detect.hpp).
+// the stored image on is the shared detection stage (detect.hpp).
 #include <algorithm>
 #include <climits>
 #include <cmath>
 
 #include "common.hpp"
-#include "dog_detect.hpp"
+#include "detect.hpp"
 
 namespace spimdecon {
 namespace {
@@ -166,6 +166,8 @@ __global__ __launch_bounds__(kDomBlock) void k_dom(Dims3 d, const float* __restr
 // FusionHelper.minMax (FusionHelper.java:87-141) as Java computes it: Math.min / Math.max
 // from Float.MAX_VALUE / -Float.MAX_VALUE, so one NaN voxel makes both NaN (the DOM image
 // is then NaN wherever the boxes fit) -- min, max and "saw a NaN" per block, then one wave.
+// Not k_minmax's rule (dog.hip: a NaN is skipped and only raises the finite flag), so the
+// two stay separate kernels.
 constexpr int kDomMmBlocks = 2048;
 constexpr float kFloatMax = 3.402823466e+38f;
 __device__ __forceinline__ void dom_mm_wave(float& mn, float& mx, int& nan) {
@@ -291,16 +293,6 @@ void dom_diameters(const spim_dom_params* p, int32_t s1[3], int32_t s2[3]) {
     }
 }
 
-void dom_check_args(const float* img, const int64_t* dims, const spim_dom_params* p) {
-    SD_CHECK(img && dims && p, SPIMDECON_ERR_ARG, "null argument");
-    SD_CHECK(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, SPIMDECON_ERR_ARG, "bad dims");
-    dom_check_params(p);
-    SD_CHECK(p->localization == 0 || p->localization == 1, SPIMDECON_ERR_ARG,
-             "localization must be 0 (none) or 1 (quadratic); the Gaussian fit is not implemented in "
-             "the reference either (Localization.java:90-96)");
-    SD_CHECK(p->ij_threads >= 1 && p->ij_threads < (1 << 20), SPIMDECON_ERR_ARG, "ij_threads must be >= 1");
-}
-
 // the DOM image (the caller's device buffer, else the workspace's) and its candidates
 void dom_run(const float* img, const int64_t* dims, const spim_dom_params* p, float* dom_out, hipStream_t s,
              DogWork& w, DogRun& r) {
@@ -324,13 +316,7 @@ void dom_run(const float* img, const int64_t* dims, const spim_dom_params* p, fl
     b.vol1 = s1[0] * s1[1] * s1[2];
     b.vol2 = s2[0] * s2[1] * s2[2];
 
-    // the view: read in place when it already lives in HBM, else one upload
-    const float* in = img;
-    if (!is_device_ptr(img, p->device)) {
-        grow(w.in, size_t(n));
-        SD_HIP(hipMemcpyAsync(w.in.p, img, n * 4, hipMemcpyDefault, s));   // host or another device
-        in = w.in.p;
-    }
+    const float* in = stage_view(w, img, n, p->device, s);
     // ProcessDOM.java:54-66 (the rule of ProcessDOG)
     grow(w.mm, 3 * 4096);   // {min, max, -, -, the per-block partials}
     static_assert(4 + 3 * kDomMmBlocks <= 3 * 4096, "partials beyond the min / max buffer");
@@ -346,12 +332,8 @@ void dom_run(const float* img, const int64_t* dims, const spim_dom_params* p, fl
         hipLaunchKernelGGL(k_dom_minmax_final, dim3(1), dim3(64), 0, s, w.mm.p + 4, nb, w.mm.p);
         SD_HIP(hipGetLastError());
     }
-    const bool out_dev = dom_out && is_device_ptr(dom_out, p->device);
-    float* domp = dom_out;
-    if (!out_dev) {
-        grow(w.dog, size_t(n));
-        domp = w.dog.p;
-    }
+    ImageDest dst(dom_out, n, p->device);
+    float* const domp = dst.store(w);
     // DOM.java:47-53: where the boxes fit; elsewhere (everywhere, when they fit nowhere) zero
     const bool interior = d.nx > 2 * b.hm[0] && d.ny > 2 * b.hm[1] && d.nz > 2 * b.hm[2];
     const unsigned gf = unsigned(std::min<int64_t>(ceil_div(d.ny * d.nz, int64_t(kDomBlock / 64)), 8192));
@@ -376,7 +358,7 @@ void dom_run(const float* img, const int64_t* dims, const spim_dom_params* p, fl
     }
     // ProcessDOM.java:104: the threshold as given (no / 10 with quadratic localisation)
     detect_stored(w, d, domp, p->threshold, p->find_min ? 1 : 0, p->find_max ? 1 : 0, p->ij_threads, s, r);
-    if (dom_out && !out_dev) SD_HIP(hipMemcpyAsync(dom_out, domp, n * 4, hipMemcpyDefault, s));
+    dst.copy_out(s);
 }
 
 }  // namespace
@@ -384,30 +366,24 @@ void dom_run(const float* img, const int64_t* dims, const spim_dom_params* p, fl
 void dom_compute(const float* img, const int64_t* dims, const spim_dom_params* p, float* dom_out, spim_peak* peaks,
                  int64_t max_peaks, int64_t* npeaks) {
     SD_CHECK(npeaks, SPIMDECON_ERR_ARG, "null argument");
-    dom_check_args(img, dims, p);
-    check_device(p->device);
-    DeviceGuard guard(p->device);
-    DogWork& w = dog_work(p->device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    StreamHolder sh(w);
-    DogRun r;
-    dom_run(img, dims, p, dom_out, sh.s, w, r);
-    peaks_to_host(r, peaks, max_peaks, npeaks, sh.s);
+    check_detector_args(img, dims, p, [&] { dom_check_params(p); });
+    with_detector(p->device, [&](DogWork& w, hipStream_t s) {
+        DogRun r;
+        dom_run(img, dims, p, dom_out, s, w, r);
+        peaks_to_host(r, peaks, max_peaks, npeaks, s);
+    });
 }
 
 // ProcessDOM.compute's result: interest points after Localization (ProcessDOM.java:107-112)
 void dom_interest_points(const float* img, const int64_t* dims, const spim_dom_params* p, float* dom_out,
                          spim_interest_point* out, int64_t max_out, int64_t* nout) {
     SD_CHECK(nout, SPIMDECON_ERR_ARG, "null argument");
-    dom_check_args(img, dims, p);
-    check_device(p->device);
-    DeviceGuard guard(p->device);
-    DogWork& w = dog_work(p->device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    StreamHolder sh(w);
-    DogRun r;
-    dom_run(img, dims, p, dom_out, sh.s, w, r);
-    points_from_peaks(w, r, p->localization, p->threshold, out, max_out, nout, sh.s);
+    check_detector_args(img, dims, p, [&] { dom_check_params(p); });
+    with_detector(p->device, [&](DogWork& w, hipStream_t s) {
+        DogRun r;
+        dom_run(img, dims, p, dom_out, s, w, r);
+        points_from_peaks(w, r, p->localization, p->threshold, out, max_out, nout, s);
+    });
 }
 
 }  // namespace spimdecon

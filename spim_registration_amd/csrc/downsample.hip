@@ -27,7 +27,7 @@
 #include <cmath>
 
 #include "common.hpp"
-#include "dog_detect.hpp"
+#include "detect.hpp"
 
 namespace spimdecon {
 namespace {
@@ -250,40 +250,26 @@ void downsample(const float* img, const int64_t* dims, const int32_t* factor, in
     SD_CHECK(dims[0] < (int64_t(1) << 30) && dims[1] < (int64_t(1) << 30) && dims[2] < (int64_t(1) << 30) &&
                  n < (int64_t(1) << 40) && dims[0] * dims[1] < (int64_t(1) << 31),
              SPIMDECON_ERR_ARG, "volume too large");
-    check_device(device);
-    DeviceGuard guard(device);
-    DogWork& w = dog_work(device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    StreamHolder sh(w);
-    hipStream_t s = sh.s;
-    // the view: read in place when it already lives in HBM, else one upload
-    const float* in = img;
-    if (!is_device_ptr(img, device)) {
-        grow(w.in, size_t(n));
-        SD_HIP(hipMemcpyAsync(w.in.p, img, n * 4, hipMemcpyDefault, s));
-        in = w.in.p;
-    }
-    const bool out_dev = is_device_ptr(out, device);
-    float* dst = out;
-    if (!out_dev) {
-        grow(w.dog, size_t(no));
-        dst = w.dog.p;
-    }
-    const bool xy = lx || ly;
-    if (!xy && !lz) {
-        SD_HIP(hipMemcpyAsync(dst, in, n * 4, hipMemcpyDeviceToDevice, s));
-    } else if (xy && lz) {
-        const int64_t mid[3] = {od[0], od[1], dims[2]};
-        grow(w.tmp_a, size_t(mid[0] * mid[1] * mid[2]));
-        launch_xy(in, dims, lx, ly, mid, w.tmp_a.p, s);
-        launch_z(w.tmp_a.p, mid[0] * mid[1], mid[2], lz, od[2], dst, s);
-    } else if (xy) {
-        launch_xy(in, dims, lx, ly, od, dst, s);
-    } else {
-        launch_z(in, dims[0] * dims[1], dims[2], lz, od[2], dst, s);
-    }
-    if (!out_dev) SD_HIP(hipMemcpyAsync(out, dst, no * 4, hipMemcpyDefault, s));
-    SD_HIP(hipStreamSynchronize(s));
+    with_detector(device, [&](DogWork& w, hipStream_t s) {
+        const float* in = stage_view(w, img, n, device, s);
+        ImageDest dest(out, no, device);
+        float* const dst = dest.store(w);
+        const bool xy = lx || ly;
+        if (!xy && !lz) {
+            SD_HIP(hipMemcpyAsync(dst, in, n * 4, hipMemcpyDeviceToDevice, s));
+        } else if (xy && lz) {
+            const int64_t mid[3] = {od[0], od[1], dims[2]};
+            grow(w.tmp_a, size_t(mid[0] * mid[1] * mid[2]));
+            launch_xy(in, dims, lx, ly, mid, w.tmp_a.p, s);
+            launch_z(w.tmp_a.p, mid[0] * mid[1], mid[2], lz, od[2], dst, s);
+        } else if (xy) {
+            launch_xy(in, dims, lx, ly, od, dst, s);
+        } else {
+            launch_z(in, dims[0] * dims[1], dims[2], lz, od[2], dst, s);
+        }
+        dest.copy_out(s);
+        SD_HIP(hipStreamSynchronize(s));
+    });
 }
 
 // DifferenceOf.java:430-444 in its own arithmetic (Math.round = floor(x + 0.5))

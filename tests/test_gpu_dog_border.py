@@ -133,7 +133,7 @@ def test_border_thin_volumes(gpu, shape):
     assert_same(pts, d, border_points(dref, 0.0, find_min=True, ij_threads=3), dref)
 
 
-# 5. the 63-tap fallback (sep_pass with the border mode)
+# 5. the 63-tap fallback (csrc/sepconv.hip: sep_pass with the border mode)
 def test_border_63_tap_fallback(gpu):
     s1, s2, _, _ = dog_ref.dog_sigmas(8.0, (0.5, 0.5, 0.5))
     assert len(dog_ref.cuda_kernels(s2)[0]) == 63

@@ -1,7 +1,8 @@
 #!/bin/bash
-# Experiment build: libspimdecon.so with one source (SRC, default dog.hip) compiled under
-# extra -D flags, the other objects reused from spim_registration_amd/_build.  Select it
-# with SPIMDECON_LIB=<path>.
+# Experiment build: libspimdecon.so with one source (SRC, default dog.hip: the fused DoG and
+# its SPIMDECON_DZ_* knobs; the candidate pass is detect.hip, the separable passes sepconv.hip)
+# compiled under extra -D flags, the other objects reused from spim_registration_amd/_build.
+# Select it with SPIMDECON_LIB=<path>.
 # usage: [SRC=fftconv.hip] tools/build_variant.sh TAG -DFOO=1 ...
 set -e
 TAG=$1; shift
