@@ -655,6 +655,96 @@ int spim_fuse_weighted_average_content(int nviews, const spim_view_source* views
                                        const double* sigma2, float* out);
 
 /* ======================================================================
+ * 8b. The bounding box estimated from the data ("Estimate automatically (experimental)") --
+ *     spim/process/fusion/boundingbox/AutomaticBoundingBox.java:36-131,
+ *     automatic/MinFilterThreshold.java:76-308, BoundingBoxGUI.java:340-399,
+ *     FusionHelper.minMax: the maximal box of all views is fused at `downsampling` (nearest
+ *     neighbour, no blending, ProcessParalell's double accumulation: section 8), a threshold is
+ *     put at `background` percent of the fused image's range, a separable minimum filter
+ *     (x, y, z; window 2r + 1 over a zero extension) erodes beads and debris, and the box of
+ *     what stays above the threshold is scaled back and padded by 3 * (size / 2).
+ *     Math.min / Math.max semantics throughout (a NaN spreads, -0 < +0): every image result
+ *     is bit-exact against the reference's arithmetic.  Images are x-fastest float32, dims
+ *     (x, y, z); img / out / filtered may be host or device pointers (as spim_dom_*).
+ * ====================================================================== */
+#define SPIM_MIN_FILTER_MAX_RADIUS 64   /* the dialog's sliders need up to 50 */
+
+/* The maximal box: per view the 8 corners of [0, dim - 1] through its row-major 3x4 model
+ * (dims: nviews x 3, models: nviews x 12), min / max over the views, Math.round;
+ * bb_dims = bb_max - bb_min + 1; fused_dims (may be NULL) = bb_dims / downsampling (integer
+ * division, BoundingBoxGUI.getDimensions).  SPIMDECON_ERR_ARG for a non-finite model,
+ * dims < 1 or downsampling < 1.  Host only: needs no GPU. */
+int spim_max_bounding_box(int nviews, const int64_t* dims, const double* models, int downsampling,
+                          int64_t bb_min[3], int64_t bb_max[3], int64_t bb_dims[3], int64_t fused_dims[3]);
+
+/* FusionHelper.minMax: Math.min / Math.max from +-Float.MAX_VALUE over every voxel. */
+int spim_min_max(const float* img, const int64_t dims[3], int device, float* min, float* max);
+
+/* MinFilterThreshold.computeLazyMinFilter with one radius for the three axes; out == img is
+ * allowed.  radius: 1 .. SPIM_MIN_FILTER_MAX_RADIUS, anything else is SPIMDECON_ERR_ARG.  Two
+ * volumes of scratch live in the workspace of spim_bbox_release_workspace. */
+int spim_min_filter(const float* img, const int64_t dims[3], int radius, int device, float* out);
+
+/* MinFilterThreshold.computeBoundingBox: per axis the smallest and largest index of the voxels
+ * with (double)v > threshold.  With no such voxel the reference's integers come back
+ * (bounds_min = dims, bounds_max = 0) and *found = 0. */
+int spim_threshold_bounds(const float* img, const int64_t dims[3], double threshold, int device,
+                          int64_t bounds_min[3], int64_t bounds_max[3], int32_t* found);
+
+typedef struct spim_segment_result {
+    float   min, max;        /* of the image (before the filter)                            */
+    double  threshold;       /* (double)(max - min) * (background / 100.0) + (double)min     */
+    int64_t bounds_min[3];   /* as spim_threshold_bounds, of the filtered image             */
+    int64_t bounds_max[3];
+    int32_t found;
+    int32_t reserved[3];
+} spim_segment_result;
+
+/* min / max -> threshold -> minimum filter -> box in one call.  filtered (may be NULL)
+ * receives the filtered image (the reference's "Display image used for segmentation");
+ * without it the z pass of the filter only feeds the box and nothing image-sized is written
+ * beyond the two scratch volumes.  background: inside (0, 100), in percent. */
+int spim_segment_bounds(const float* img, const int64_t dims[3], double background, int radius, int device,
+                        float* filtered, spim_segment_result* res);
+
+typedef struct spim_autobbox_params {
+    double background;             /* percent of the range; default 5                        */
+    int    discarded_object_size;  /* default 25; radiusMin = size / 2                        */
+    int    downsampling;           /* default 4; the filter runs at max(radiusMin / ds, 1)    */
+    int    device;
+    int    src_on_device;          /* 1: views[].img are device pointers                      */
+    int    reserved[8];
+} spim_autobbox_params;
+
+void spim_autobbox_params_default(spim_autobbox_params* p);
+
+typedef struct spim_autobbox_result {
+    int64_t bb_min[3];       /* the estimate, world voxels: bounds * ds + max_min -+ 3 radiusMin */
+    int64_t bb_max[3];       /* (not clamped to the maximal box, as the reference)           */
+    int64_t bb_dims[3];      /* bb_max - bb_min + 1                                           */
+    int32_t found;           /* 0: nothing above the threshold; bb_* then hold the reference's */
+    int32_t radius_min;      /*    inverted box and must not be used                          */
+    int32_t eff_radius;
+    int32_t reserved;
+    int64_t max_min[3];      /* the maximal box                                               */
+    int64_t max_max[3];
+    int64_t max_dims[3];
+    int64_t fused_dims[3];   /* max_dims / downsampling                                       */
+    spim_segment_result seg; /* of the fused image                                            */
+} spim_autobbox_result;
+
+/* AutomaticBoundingBox.queryParameters + MinFilterThreshold.run over nviews views: the
+ * maximal box, its fusion into device memory (spim_fuse_weighted_average, interpolation 0,
+ * no blending), spim_segment_bounds on it.  An effective radius above
+ * SPIM_MIN_FILTER_MAX_RADIUS and a downsampling that leaves no voxel are SPIMDECON_ERR_ARG.
+ * Not restated: "Load input images sequentially" (ProcessSequential accumulates in float). */
+int spim_auto_bounding_box(int nviews, const spim_view_source* views, const spim_autobbox_params* p,
+                           spim_autobbox_result* res);
+
+/* frees device `device`'s scratch of this section (the next call allocates it again) */
+int spim_bbox_release_workspace(int device);
+
+/* ======================================================================
  * 9. PSF extraction / transformation --
  *    spim/process/fusion/deconvolution/ExtractPSF.java.  All buffers are
  *    x-fastest float32 in host memory unless stated; dims are (x, y, z).

@@ -127,6 +127,24 @@ class FusionParams(C.Structure):
                 ("src_on_device", C.c_int), ("out_on_device", C.c_int), ("reserved", C.c_int * 8)]
 
 
+class SegmentResult(C.Structure):
+    _fields_ = [("min", C.c_float), ("max", C.c_float), ("threshold", C.c_double),
+                ("bounds_min", C.c_int64 * 3), ("bounds_max", C.c_int64 * 3), ("found", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class AutoBBoxParams(C.Structure):
+    _fields_ = [("background", C.c_double), ("discarded_object_size", C.c_int), ("downsampling", C.c_int),
+                ("device", C.c_int), ("src_on_device", C.c_int), ("reserved", C.c_int * 8)]
+
+
+class AutoBBoxResult(C.Structure):
+    _fields_ = [("bb_min", C.c_int64 * 3), ("bb_max", C.c_int64 * 3), ("bb_dims", C.c_int64 * 3),
+                ("found", C.c_int32), ("radius_min", C.c_int32), ("eff_radius", C.c_int32),
+                ("reserved", C.c_int32), ("max_min", C.c_int64 * 3), ("max_max", C.c_int64 * 3),
+                ("max_dims", C.c_int64 * 3), ("fused_dims", C.c_int64 * 3), ("seg", SegmentResult)]
+
+
 class InterestPointC(C.Structure):
     _fields_ = [("pos", C.c_double * 3), ("intensity", C.c_float), ("is_max", C.c_int32)]
 
@@ -221,6 +239,17 @@ SIGNATURES = {
                                  C.c_int, C.c_float]),
     "spim_input_params_default": (None, [C.POINTER(InputParams)]),
     "spim_fusion_params_default": (None, [C.POINTER(FusionParams)]),
+    "spim_max_bounding_box": (C.c_int, [C.c_int, _pi64, _pd, C.c_int, _pi64, _pi64, _pi64, _pi64]),
+    "spim_min_max": (C.c_int, [C.c_void_p, _pi64, C.c_int, _pf, _pf]),
+    "spim_min_filter": (C.c_int, [C.c_void_p, _pi64, C.c_int, C.c_int, C.c_void_p]),
+    "spim_threshold_bounds": (C.c_int, [C.c_void_p, _pi64, C.c_double, C.c_int, _pi64, _pi64,
+                                        C.POINTER(C.c_int32)]),
+    "spim_segment_bounds": (C.c_int, [C.c_void_p, _pi64, C.c_double, C.c_int, C.c_int, C.c_void_p,
+                                      C.POINTER(SegmentResult)]),
+    "spim_autobbox_params_default": (None, [C.POINTER(AutoBBoxParams)]),
+    "spim_auto_bounding_box": (C.c_int, [C.c_int, C.POINTER(ViewSource), C.POINTER(AutoBBoxParams),
+                                         C.POINTER(AutoBBoxResult)]),
+    "spim_bbox_release_workspace": (C.c_int, [C.c_int]),
     "spim_psf_transformed_size": (C.c_int, [_pi64, _pd, _pi64, _pd]),
     "spim_transform_psf": (C.c_int, [_pf, _pi64, _pd, _pf, C.c_int]),
     "spim_extract_psf": (C.c_int, [C.c_void_p, _pi64, C.c_int, _pd, C.c_int64, _pi64, _pd, _pf, _pf, C.c_int]),

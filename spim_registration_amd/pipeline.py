@@ -54,6 +54,7 @@ class TimepointResult:
     stage_digests: dict = field(default_factory=dict)   # SHA-256 per stage output (digest=True)
     models: list = field(default_factory=list)   # the view models used (refined when refine is set)
     globalopt: object = None                     # globalopt.GlobalOptResult (refine is set)
+    bounding_box: tuple = None                   # (bb_min, bb_dims) used, (x, y, z) (estimated for bb_min="auto")
 
 
 def apply_model(model, pts):
@@ -105,7 +106,7 @@ def corresponding_detections(points, models, radius: float = 2.0, device=None):
     return out
 
 
-def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), iterations: int = 10,
+def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 25), iterations: int = 10,
                       psftype: PSFTYPE = PSFTYPE.OPTIMIZATION_I, lam: float = 0.006, sigma: float = 1.8,
                       threshold: float = 0.008, localization: int = 1, radius: float = 2.0,
                       blending_border=(-8, -8, -8), blending_range=(12, 12, 12),
@@ -120,9 +121,13 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
                       icp_max_distance: float = 5.0, icp_max_iterations: int = 100,
                       downsample_xy=1, downsample_z: int = 1, voxel_size=None,
                       max_detections: int | None = None,
-                      max_detections_type: str = "brightest") -> TimepointResult:
+                      max_detections_type: str = "brightest", auto_bb: dict | None = None) -> TimepointResult:
     """views: per view a [z, y, x] float32 torch tensor on the GPU (the acquired
-    stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z);
+    stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z), or bb_min="auto"
+    (bb_dims None): the box is estimated from the views under the models the input preparation
+    uses (``boundingbox.auto_bounding_box`` with the keywords of ``auto_bb``: background,
+    discarded_object_size, downsampling), logged, recorded in ``bounding_box`` and timed as
+    ``ms["auto_bounding_box"]``; ValueError when nothing is found;
     dog_extension: the detect stage's 'mirror' (accurate) or 'border' (approximate) GPU
     mode (``dog.compute``); detector: 'dog' (Difference-of-Gaussian: sigma) or 'dom'
     (Difference-of-Mean: radius1 / radius2, ``dom.compute``), both with threshold and
@@ -155,6 +160,14 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
         raise ValueError(f"detector must be 'dog' or 'dom', not {detector!r}")
     if matching not in ("nearest", "rgldm", "geometric_hashing"):
         raise ValueError(f"matching must be 'nearest', 'rgldm' or 'geometric_hashing', not {matching!r}")
+    auto = isinstance(bb_min, str)
+    if auto:
+        if bb_min != "auto":
+            raise ValueError(f"bb_min must be (x, y, z) or 'auto', not {bb_min!r}")
+        if bb_dims is not None:
+            raise ValueError("bb_min='auto' estimates bb_dims too: pass bb_dims=None")
+    elif auto_bb is not None or bb_dims is None:
+        raise ValueError("an explicit bb_min needs bb_dims and no auto_bb (auto_bb goes with bb_min='auto')")
     ms = {}
 
     def lap(name, t0):
@@ -228,6 +241,12 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
         t = lap("register", t)
     corr = corresponding_detections(points, models, radius, device=f"cuda:{device}")   # 2. (registration given)
     t = lap("correspondences", t)
+    if auto:   # 2b. "Estimate automatically": the box from the data, under the models used below
+        from . import boundingbox
+        bb_min, bb_dims = boundingbox.auto_bounding_box(list(views), models, device=device, **(auto_bb or {}))
+        if log:
+            log(f"automatic bounding box: min {bb_min}, dims {bb_dims}")
+        t = lap("auto_bounding_box", t)
     imgs, ws, info = input_prep.prepare_inputs(views, models, bb_min, bb_dims, blending_border, blending_range,
                                                weight_type, device=device)   # 3a.
     t = lap("prepare_inputs", t)
@@ -269,7 +288,8 @@ def process_timepoint(views, models, bb_min, bb_dims, *, psf_size=(19, 19, 25), 
         sess.close()
     del imgs, ws
     lap("rl_result", t)
-    return TimepointResult(psi, points, corr, psfs, stats, ms, engine, sd, models, gres)
+    return TimepointResult(psi, points, corr, psfs, stats, ms, engine, sd, models, gres,
+                           (tuple(int(x) for x in bb_min), tuple(int(x) for x in bb_dims)))
 
 
 def _sha(parts) -> str:
@@ -293,7 +313,7 @@ class Pipeline:
     def __init__(self, **params):
         self.params = params
 
-    def process(self, views, models, bb_min, bb_dims, log=None, digest=False) -> TimepointResult:
+    def process(self, views, models, bb_min, bb_dims=None, log=None, digest=False) -> TimepointResult:
         return process_timepoint(views, models, bb_min, bb_dims, log=log, digest=digest, **self.params)
 
 
