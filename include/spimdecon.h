@@ -745,6 +745,86 @@ int spim_auto_bounding_box(int nviews, const spim_view_source* views, const spim
 int spim_bbox_release_workspace(int device);
 
 /* ======================================================================
+ * 8b. The bounding box from the interest points, "Automatically reorientate and estimate based
+ *     on sample features" -- spim/process/fusion/boundingbox/AutomaticReorientation.java:277-573
+ *     with the vendored vecmath (Transform3D.java:1397-1450, :4755-4765, Vector3d.java:127-166).
+ *     All arithmetic is double in the reference's order, no multiply and add contracted; every
+ *     result is bit-exact against that arithmetic with the host's libm for sqrt, acos, sin and
+ *     cos (the payload of a NaN is not pinned).  Point lists are (n, 3) doubles (x, y, z), host
+ *     or device memory; non-finite coordinates (as double or as float), a null list with a
+ *     positive count and more than 2^31 - 1 points are SPIMDECON_ERR_ARG, the message led by the
+ *     call's name.
+ * ====================================================================== */
+
+/* the farthest-pair kernel's tile: row points per block = column points per LDS tile.  Host
+ * only: needs no GPU. */
+void spim_reorient_tile(int32_t* tile);
+
+/* determineOptimalBoundingBox :316-343 over all n (n - 1) / 2 pairs: *d2 = the largest squared
+ * distance (dx * dx + dy * dy + dz * dz of a - b), (*i, *j) = the indices of the reference's p1
+ * and p2: the first pair in (i, j) scan order among those at that distance, ordered so that
+ * p1.x <= p2.x -- except when it is the start pair (0, 1), which the reference never reorders.
+ * n < 2 is SPIMDECON_ERR_ARG (the reference fails on points.get(1)). */
+int spim_farthest_pair(const double* pts, int64_t n, int device, int32_t* i, int32_t* j, double* d2);
+
+/* testAxis :429-442 under m (1 .. 27) given transforms at once: mats holds m row-major 3x4
+ * doubles (host memory); every point goes through Transform3D.transform, per row
+ * ((m0 x + m1 y) + m2 z) + m3, and out6m[6 k ..] = min x, y, z, max x, y, z under matrix k by
+ * Math.min / Math.max from +-Double.MAX_VALUE (a NaN spreads: a matrix of NaNs gives NaNs for
+ * that matrix only; -0 < +0).  n >= 1. */
+int spim_axis_boxes(const double* pts, int64_t n, const double* mats, int m, int device, double* out6m);
+
+/* determineSizeSimple :488-512: min x, y, z, max x, y, z of the coordinates as they are (no
+ * transform: a -0 stays -0).  n >= 1. */
+int spim_points_min_max(const double* pts, int64_t n, int device, double* out6);
+
+typedef struct spim_reorient_params {
+    int32_t use_corresponding;  /* 1 (the dialog's default): only detections corr[v][k] of list v  */
+    int32_t reorientate;        /* 1: the minimal-volume rotation; 0: the dialog's fourth choice,  */
+                                /*    the identity and determineSizeSimple                         */
+    double  percent;            /* "Additional size [%]" of the largest padding; default 10        */
+    int32_t device;
+    int32_t far_split;          /* 0 = auto; >0 forces the partitions of the column tiles (tests)  */
+    int32_t reserved[8];
+} spim_reorient_params;
+
+void spim_reorient_params_default(spim_reorient_params* p);
+
+typedef struct spim_reorient_result {
+    double  transform[12];   /* row-major 3x4, to preconcatenate to every view's model            */
+    double  min_f[3];        /* the box of the world points under transform, before the padding   */
+    double  max_f[3];
+    int64_t bb_min[3];       /* (int) Math.round(min_f - add); add = the largest over the axes of */
+    int64_t bb_max[3];       /* (max_f - min_f) * (percent / 100.0) / 2; Math.round(max_f + add)  */
+    int64_t bb_dims[3];      /* bb_max - bb_min + 1                                               */
+    int64_t n_points;        /* world points used                                                 */
+    int32_t far_i, far_j;    /* as spim_farthest_pair, indices into the concatenated world points */
+    double  far_d2;          /* (-1, -1, 0 with reorientate 0)                                    */
+    double  start_volume;    /* testAxis of the farthest pair's direction (the reference logs it) */
+    double  min_volume;      /* of min_f / max_f: the smallest over the 8 x 27 candidates         */
+    double  axis[3];         /* the search vector the transform maps onto the x axis              */
+} spim_reorient_result;
+
+/* getAllDetectionsInGlobalCoordinates, then determineOptimalBoundingBox (or determineSizeSimple)
+ * and :277-289.  lists[v] (counts[v] points, view pixels) goes through models[12 v ..] (row-major
+ * 3x4, host memory) row by row ((m0 x + m1 y) + m2 z) + m3; the views are concatenated in order.
+ * With use_corresponding only the detections corr[v][0 .. corr_counts[v]) of list v are taken, in
+ * that order (int64 indices, host or device memory; one out of range is SPIMDECON_ERR_ARG);
+ * without it corr and corr_counts may be NULL.  The search: from the farthest pair's direction,
+ * the steps 0.4 .. 0.001, per step the 27 candidates in zi, yi, xi order about the step's
+ * start vector in one spim_axis_boxes launch, a candidate taken on a strictly smaller volume.
+ * Deviation: fewer than two world points (one with reorientate 0) are SPIMDECON_ERR_ARG -- the
+ * reference stops at none and fails on points.get(1) at one.  A box beyond the int range and
+ * world coordinates that are not finite are SPIMDECON_ERR_ARG. */
+int spim_reorient_bounding_box(int n_views, const double* const* lists, const int64_t* counts,
+                               const int64_t* const* corr, const int64_t* corr_counts,
+                               const double* models, const spim_reorient_params* params,
+                               spim_reorient_result* result);
+
+/* frees device `device`'s scratch of this section (the next call allocates it again) */
+int spim_reorient_release_workspace(int device);
+
+/* ======================================================================
  * 9. PSF extraction / transformation --
  *    spim/process/fusion/deconvolution/ExtractPSF.java.  All buffers are
  *    x-fastest float32 in host memory unless stated; dims are (x, y, z).

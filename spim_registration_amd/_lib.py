@@ -145,6 +145,18 @@ class AutoBBoxResult(C.Structure):
                 ("max_dims", C.c_int64 * 3), ("fused_dims", C.c_int64 * 3), ("seg", SegmentResult)]
 
 
+class ReorientParams(C.Structure):
+    _fields_ = [("use_corresponding", C.c_int32), ("reorientate", C.c_int32), ("percent", C.c_double),
+                ("device", C.c_int32), ("far_split", C.c_int32), ("reserved", C.c_int32 * 8)]
+
+
+class ReorientResult(C.Structure):
+    _fields_ = [("transform", C.c_double * 12), ("min_f", C.c_double * 3), ("max_f", C.c_double * 3),
+                ("bb_min", C.c_int64 * 3), ("bb_max", C.c_int64 * 3), ("bb_dims", C.c_int64 * 3),
+                ("n_points", C.c_int64), ("far_i", C.c_int32), ("far_j", C.c_int32), ("far_d2", C.c_double),
+                ("start_volume", C.c_double), ("min_volume", C.c_double), ("axis", C.c_double * 3)]
+
+
 class InterestPointC(C.Structure):
     _fields_ = [("pos", C.c_double * 3), ("intensity", C.c_float), ("is_max", C.c_int32)]
 
@@ -250,6 +262,14 @@ SIGNATURES = {
     "spim_auto_bounding_box": (C.c_int, [C.c_int, C.POINTER(ViewSource), C.POINTER(AutoBBoxParams),
                                          C.POINTER(AutoBBoxResult)]),
     "spim_bbox_release_workspace": (C.c_int, [C.c_int]),
+    "spim_reorient_tile": (None, [C.POINTER(_i32)]),
+    "spim_farthest_pair": (C.c_int, [C.c_void_p, _i64, C.c_int, C.POINTER(_i32), C.POINTER(_i32), _pd]),
+    "spim_axis_boxes": (C.c_int, [C.c_void_p, _i64, _pd, C.c_int, C.c_int, _pd]),
+    "spim_points_min_max": (C.c_int, [C.c_void_p, _i64, C.c_int, _pd]),
+    "spim_reorient_params_default": (None, [C.POINTER(ReorientParams)]),
+    "spim_reorient_bounding_box": (C.c_int, [C.c_int, C.POINTER(C.c_void_p), _pi64, C.POINTER(C.c_void_p), _pi64,
+                                             _pd, C.POINTER(ReorientParams), C.POINTER(ReorientResult)]),
+    "spim_reorient_release_workspace": (C.c_int, [C.c_int]),
     "spim_psf_transformed_size": (C.c_int, [_pi64, _pd, _pi64, _pd]),
     "spim_transform_psf": (C.c_int, [_pf, _pi64, _pd, _pf, C.c_int]),
     "spim_extract_psf": (C.c_int, [C.c_void_p, _pi64, C.c_int, _pd, C.c_int64, _pi64, _pd, _pf, _pf, C.c_int]),

@@ -12,6 +12,13 @@ The fused image never leaves the GPU; every image-sized step is a kernel of
 a NaN spreads, -0 < +0).  Not restated: "Load input images sequentially" (ProcessSequential's
 float accumulation).
 
+"Automatically reorientate and estimate based on sample features"
+(boundingbox/AutomaticReorientation.java) takes the box from the interest points instead:
+``reorient_bounding_box`` finds the rotation under which the detections' axis-aligned box is
+smallest (the farthest pair over all pairs, then a search over 8 x 27 axes; ``csrc/reorient.hip``,
+all double and bit-exact against the reference's arithmetic) and returns it with the models it
+is preconcatenated to and the padded box.
+
 Images are [z, y, x] float32, numpy arrays or torch tensors on the GPU (read in place; image
 results come back as what went in); boxes, dims and positions are (x, y, z).
 """
@@ -25,7 +32,9 @@ from . import _lib
 from ._lib import check
 
 __all__ = ["max_bounding_box", "min_max", "min_filter", "threshold_bounds", "segment_bounds",
-           "auto_bounding_box", "release_workspace", "MAX_RADIUS"]
+           "auto_bounding_box", "release_workspace", "MAX_RADIUS", "farthest_pair", "axis_boxes",
+           "points_min_max", "preconcatenate", "reorient_bounding_box", "reorient_tile",
+           "release_reorient_workspace"]
 
 MAX_RADIUS = 64      # SPIM_MIN_FILTER_MAX_RADIUS
 
@@ -198,3 +207,130 @@ def auto_bounding_box(views, models, background: float = 5.0, discarded_object_s
 def release_workspace(device: int = 0) -> None:
     """Frees the device's scratch volumes of this module (the next call allocates them again)."""
     check(_lib.load().spim_bbox_release_workspace(int(device)))
+
+
+# ---------------------------------------------------------------- the box from the interest points
+def _points(x):
+    """(pointer, n, the object that owns the memory) of an (n, 3) double array: a numpy array
+    or a CUDA torch tensor (read in place)."""
+    if _on_gpu(x):
+        import torch
+        if x.dim() != 2 or x.shape[1] != 3:
+            raise ValueError("points must be (n, 3)")
+        x = x.contiguous().double()
+        torch.cuda.synchronize(x.device)   # the library runs on its own stream
+        return C.c_void_p(x.data_ptr()), int(x.shape[0]), x
+    a = np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1, 3))
+    return C.c_void_p(a.ctypes.data), len(a), a
+
+
+def reorient_tile() -> int:
+    """Row points per block = column points per LDS tile of the farthest-pair kernel."""
+    t = C.c_int32(0)
+    _lib.load().spim_reorient_tile(C.byref(t))
+    return int(t.value)
+
+
+def farthest_pair(points, device: int = 0):
+    """AutomaticReorientation.determineOptimalBoundingBox :316-343 over (n, 3) points (a numpy
+    array or a CUDA torch tensor): (i, j, d2), the indices of the reference's p1 and p2 and
+    their squared distance.  Among the pairs at the largest distance the first in (i, j) scan
+    order wins; it is ordered so that p1.x <= p2.x unless it is the start pair (0, 1)."""
+    lib = _lib.load()
+    ptr, n, _keep = _points(points)
+    i, j, d2 = C.c_int32(-1), C.c_int32(-1), C.c_double(0.0)
+    check(lib.spim_farthest_pair(ptr, n, int(device), C.byref(i), C.byref(j), C.byref(d2)))
+    return int(i.value), int(j.value), float(d2.value)
+
+
+def axis_boxes(points, matrices, device: int = 0):
+    """testAxis :429-442 under up to 27 transforms at once: ``matrices`` (m, 3, 4); returns
+    (m, 6) float64, per matrix min x, y, z, max x, y, z of the transformed points by Math.min /
+    Math.max (a matrix of NaNs gives NaNs for that matrix only)."""
+    lib = _lib.load()
+    ptr, n, _keep = _points(points)
+    mats = np.ascontiguousarray(np.asarray(matrices, np.float64).reshape(-1, 12))
+    out = np.empty((len(mats), 6), np.float64)
+    check(lib.spim_axis_boxes(ptr, n, mats.ctypes.data_as(_lib._pd), len(mats), int(device),
+                              out.ctypes.data_as(_lib._pd)))
+    return out
+
+
+def points_min_max(points, device: int = 0):
+    """determineSizeSimple :488-512: (6,) float64, min x, y, z, max x, y, z of the points."""
+    lib = _lib.load()
+    ptr, n, _keep = _points(points)
+    out = np.empty(6, np.float64)
+    check(lib.spim_points_min_max(ptr, n, int(device), out.ctypes.data_as(_lib._pd)))
+    return out
+
+
+def preconcatenate(transform, model):
+    """transform o model, both 3x4: what ``ViewRegistration.preconcatenateTransform`` leaves as
+    the view's model.  Every element is the left-to-right sum t0 * m0 + t1 * m1 + t2 * m2 (+ t3
+    in the last column)."""
+    t = np.asarray(transform, np.float64).reshape(3, 4)
+    m = np.asarray(model, np.float64).reshape(3, 4)
+    out = np.empty((3, 4))
+    for r in range(3):
+        for c in range(4):
+            s = t[r, 0] * m[0, c] + t[r, 1] * m[1, c] + t[r, 2] * m[2, c]
+            out[r, c] = s + t[r, 3] if c == 3 else s
+    return out
+
+
+def reorient_bounding_box(points, models, corresponding=None, percent: float = 10.0, reorientate: bool = True,
+                          device: int = 0, return_details: bool = False, far_split: int = 0):
+    """"Automatically reorientate and estimate based on sample features"
+    (AutomaticReorientation.java): ``points`` per view (n, 3) detections in view pixels (numpy
+    arrays or CUDA torch tensors), ``models`` per view 3x4 (view -> world); ``corresponding``:
+    per view the indices of the detections to use (the dialog's "only corresponding
+    detections"), None = all.  The world points' axis-aligned box has minimal volume under the
+    rotation returned; it is padded by ``percent`` of its largest extent (half on each side).
+    Returns (transform, new_models, bb_min, bb_dims): the 3x4 rotation, ``new_models[v] =
+    transform o models[v]`` (``preconcatenate``) and the box, (x, y, z) tuples ready for
+    ``prepare_inputs`` / ``process_timepoint`` with the new models.  ``reorientate=False``: the
+    identity and the plain min / max of the world points.  ``return_details``: a fifth value, a
+    dict with min_f, max_f, bb_max, n_points, far_pair (i, j into the concatenated world points),
+    far_d2, start_volume, min_volume and axis.  Fewer than two points (one without reorientate)
+    are an error.  ``far_split`` forces the farthest-pair kernel's column partitions (0 = auto;
+    the result does not depend on it)."""
+    lib = _lib.load()
+    V = len(points)
+    if V < 1 or len(models) != V or (corresponding is not None and len(corresponding) != V):
+        raise ValueError("need one model (and one index list) per view")
+    staged = [_points(p) for p in points]
+    lists = (C.c_void_p * V)(*[s[0] for s in staged])
+    counts = (C.c_int64 * V)(*[s[1] for s in staged])
+    m = np.ascontiguousarray(np.stack([np.asarray(x, np.float64).reshape(12) for x in models]))
+    corr = cc = None
+    if corresponding is not None:
+        idx = [np.ascontiguousarray(np.asarray(c.cpu() if hasattr(c, "cpu") else c).reshape(-1), np.int64)
+               for c in corresponding]
+        corr = (C.c_void_p * V)(*[C.c_void_p(i.ctypes.data) for i in idx])
+        cc = (C.c_int64 * V)(*[len(i) for i in idx])
+    p = _lib.ReorientParams()
+    lib.spim_reorient_params_default(C.byref(p))
+    p.use_corresponding = int(corresponding is not None)
+    p.reorientate = int(bool(reorientate))
+    p.percent = float(percent)
+    p.device = int(device)
+    p.far_split = int(far_split)
+    r = _lib.ReorientResult()
+    check(lib.spim_reorient_bounding_box(V, lists, counts, corr, cc, m.ctypes.data_as(_lib._pd), C.byref(p),
+                                         C.byref(r)))
+    transform = np.array(r.transform[:], np.float64).reshape(3, 4)
+    new_models = [preconcatenate(transform, x) for x in models]
+    t = lambda a: tuple(int(x) for x in a)
+    out = (transform, new_models, t(r.bb_min), t(r.bb_dims))
+    if return_details:
+        out += ({"min_f": np.array(r.min_f[:]), "max_f": np.array(r.max_f[:]), "bb_max": t(r.bb_max),
+                 "n_points": int(r.n_points), "far_pair": (int(r.far_i), int(r.far_j)), "far_d2": float(r.far_d2),
+                 "start_volume": float(r.start_volume), "min_volume": float(r.min_volume),
+                 "axis": np.array(r.axis[:])},)
+    return out
+
+
+def release_reorient_workspace(device: int = 0) -> None:
+    """Frees the device's scratch of the interest-point box (the next call allocates it again)."""
+    check(_lib.load().spim_reorient_release_workspace(int(device)))

@@ -55,6 +55,7 @@ class TimepointResult:
     models: list = field(default_factory=list)   # the view models used (refined when refine is set)
     globalopt: object = None                     # globalopt.GlobalOptResult (refine is set)
     bounding_box: tuple = None                   # (bb_min, bb_dims) used, (x, y, z) (estimated for bb_min="auto")
+    reorientation: object = None                 # bb_min="reorient": the 3x4 transform preconcatenated to ``models``
 
 
 def apply_model(model, pts):
@@ -121,13 +122,21 @@ def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 
                       icp_max_distance: float = 5.0, icp_max_iterations: int = 100,
                       downsample_xy=1, downsample_z: int = 1, voxel_size=None,
                       max_detections: int | None = None,
-                      max_detections_type: str = "brightest", auto_bb: dict | None = None) -> TimepointResult:
+                      max_detections_type: str = "brightest", auto_bb: dict | None = None,
+                      reorient: dict | None = None) -> TimepointResult:
     """views: per view a [z, y, x] float32 torch tensor on the GPU (the acquired
     stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z), or bb_min="auto"
     (bb_dims None): the box is estimated from the views under the models the input preparation
     uses (``boundingbox.auto_bounding_box`` with the keywords of ``auto_bb``: background,
     discarded_object_size, downsampling), logged, recorded in ``bounding_box`` and timed as
-    ``ms["auto_bounding_box"]``; ValueError when nothing is found;
+    ``ms["auto_bounding_box"]``; ValueError when nothing is found; or bb_min="reorient" (bb_dims
+    None): after the correspondences stage ``boundingbox.reorient_bounding_box`` finds, from
+    ``points`` and -- unless ``reorient`` says ``corresponding=False`` -- only their corresponding
+    detections (the dialog's default), the rotation under which the detections' box is smallest;
+    the transform is preconcatenated to the models that input preparation and PSF extraction use
+    (``models`` of the result), kept in ``reorientation``, the padded box (``reorient``:
+    percent, default 10; reorientate) logged, recorded in ``bounding_box`` and timed as
+    ``ms["reorient_bounding_box"]``;
     dog_extension: the detect stage's 'mirror' (accurate) or 'border' (approximate) GPU
     mode (``dog.compute``); detector: 'dog' (Difference-of-Gaussian: sigma) or 'dom'
     (Difference-of-Mean: radius1 / radius2, ``dom.compute``), both with threshold and
@@ -160,14 +169,18 @@ def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 
         raise ValueError(f"detector must be 'dog' or 'dom', not {detector!r}")
     if matching not in ("nearest", "rgldm", "geometric_hashing"):
         raise ValueError(f"matching must be 'nearest', 'rgldm' or 'geometric_hashing', not {matching!r}")
-    auto = isinstance(bb_min, str)
-    if auto:
-        if bb_min != "auto":
-            raise ValueError(f"bb_min must be (x, y, z) or 'auto', not {bb_min!r}")
+    estimated = isinstance(bb_min, str)
+    auto = estimated and bb_min == "auto"
+    if estimated:
+        if bb_min not in ("auto", "reorient"):
+            raise ValueError(f"bb_min must be (x, y, z), 'auto' or 'reorient', not {bb_min!r}")
         if bb_dims is not None:
-            raise ValueError("bb_min='auto' estimates bb_dims too: pass bb_dims=None")
-    elif auto_bb is not None or bb_dims is None:
-        raise ValueError("an explicit bb_min needs bb_dims and no auto_bb (auto_bb goes with bb_min='auto')")
+            raise ValueError(f"bb_min={bb_min!r} estimates bb_dims too: pass bb_dims=None")
+        if (auto_bb is not None and not auto) or (reorient is not None and auto):
+            raise ValueError("auto_bb goes with bb_min='auto', reorient with bb_min='reorient'")
+    elif auto_bb is not None or reorient is not None or bb_dims is None:
+        raise ValueError("an explicit bb_min needs bb_dims and no auto_bb / reorient (they go with bb_min='auto' / "
+                         "'reorient')")
     ms = {}
 
     def lap(name, t0):
@@ -247,6 +260,17 @@ def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 
         if log:
             log(f"automatic bounding box: min {bb_min}, dims {bb_dims}")
         t = lap("auto_bounding_box", t)
+    reorientation = None
+    if estimated and not auto:   # 2c. "Automatically reorientate and estimate based on sample features"
+        from . import boundingbox
+        ro = dict(reorient or {})
+        use_corr = ro.pop("corresponding", True)
+        reorientation, models, bb_min, bb_dims = boundingbox.reorient_bounding_box(
+            points, models, corresponding=corr if use_corr else None, device=device, **ro)
+        if log:
+            log(f"reorienting bounding box: min {bb_min}, dims {bb_dims}, transform "
+                f"{[round(float(x), 6) for x in reorientation.reshape(12)]}")
+        t = lap("reorient_bounding_box", t)
     imgs, ws, info = input_prep.prepare_inputs(views, models, bb_min, bb_dims, blending_border, blending_range,
                                                weight_type, device=device)   # 3a.
     t = lap("prepare_inputs", t)
@@ -289,7 +313,7 @@ def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 
     del imgs, ws
     lap("rl_result", t)
     return TimepointResult(psi, points, corr, psfs, stats, ms, engine, sd, models, gres,
-                           (tuple(int(x) for x in bb_min), tuple(int(x) for x in bb_dims)))
+                           (tuple(int(x) for x in bb_min), tuple(int(x) for x in bb_dims)), reorientation)
 
 
 def _sha(parts) -> str:
