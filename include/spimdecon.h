@@ -647,6 +647,12 @@ int spim_fuse_weighted_average(int nviews, const spim_view_source* views, const 
 int spim_content_based_weights(const float* img, const int64_t dims[3], const double sigma1[3],
                                const double sigma2[3], float* out, int device);
 
+/* The tiling of the content-weight kernels, for tests that straddle it: outputs per line and
+ * block along the pass axis, lines per block, taps per register-window step (the taps are
+ * zero-padded to a multiple), the tap limit, and the threads per block and the blocks of the
+ * min / max reduction.  Needs no GPU. */
+void spim_content_tiles(int32_t sizes[6]);
+
 /* spim_fuse_weighted_average with the content weight of every view (sigma1 / sigma2: nviews x 3)
  * multiplied into its blending weight (p->use_blending 1) or used alone (0) */
 int spim_fuse_weighted_average_content(int nviews, const spim_view_source* views,

@@ -389,6 +389,12 @@ void content_based_weights(const float* img, const int64_t* dims, const double* 
 
 using namespace spimdecon;
 
+extern "C" void spim_content_tiles(int32_t sizes[6]) {
+    if (!sizes) return;
+    const int32_t v[6] = {kCwTile, kCwLines, kCwChunk, kCwMaxTaps, kRedBlock, kRedGrid};
+    std::copy(v, v + 6, sizes);
+}
+
 extern "C" int spim_content_based_weights(const float* img, const int64_t dims[3], const double sigma1[3],
                                           const double sigma2[3], float* out, int device) {
     return guarded([&] { content_based_weights(img, dims, sigma1, sigma2, out, device); });

@@ -161,6 +161,15 @@ def content_based_weights(img, sigma1=(20, 20, 20), sigma2=(40, 40, 40), device:
     return out
 
 
+def content_tile_sizes():
+    """(outputs per line and block along the pass axis, lines per block, taps per register-
+    window step, the tap limit, threads per reduction block, reduction blocks) of the
+    content-weight kernels."""
+    sizes = (C.c_int32 * 6)()
+    _lib.load().spim_content_tiles(sizes)
+    return tuple(int(s) for s in sizes)
+
+
 def fuse_weighted_average(srcs, models, bb_min, bb_dims, downsampling: float = 1.0, interpolation: int = 1,
                           use_blending: bool = True, blending_borders=None, blending_ranges=None,
                           device: int = 0, use_content_based: bool = False, content_sigma1=None,
