@@ -412,6 +412,34 @@ int spim_dom_interest_points(const float* img, const int64_t* dims, const spim_d
                              int64_t* nout);
 
 /* ======================================================================
+ * 6b''. The detection stage on a caller's image -- everything spim_dog_* and spim_dom_* run
+ *     once their image is stored: InteractiveIntegral.findPeaks (InteractiveIntegral.java:
+ *     360-468) over img, the x % ij_threads order, and Localization (Localization.java:19-88).
+ *     img: dims {nx, ny, nz} x-fastest, host or device memory, not modified.  A voxel is a
+ *     candidate unless |v| < min_peak (InteractiveIntegral.java:409): a NaN min_peak skips
+ *     nothing, a NaN voxel is never an extremum.  Capacity rule and workspace as spim_dog_*.
+ *     Argument rules as spim_dom_* (null, dims < 1, ij_threads < 1, localization other than
+ *     0 / 1, an unknown route: SPIMDECON_ERR_ARG before any GPU work).
+ * ====================================================================== */
+#define SPIM_DETECT_ROUTE_AUTO   0   /* the library's choice, as spim_dog_* / spim_dom_* take it        */
+#define SPIM_DETECT_ROUTE_WAVE   1   /* the wave-per-62-columns kernel; SPIMDECON_ERR_ARG from 4 GiB on */
+#define SPIM_DETECT_ROUTE_APPEND 2   /* the thread-per-voxel kernel (images of 4 GiB and more)          */
+/* The extrema of the wanted kinds, in the reference's order. */
+int spim_detect_peaks(const float* img, const int64_t* dims, float min_peak, int32_t find_min,
+                      int32_t find_max, int32_t ij_threads, int32_t route, int32_t device,
+                      spim_peak* peaks, int64_t max_peaks, int64_t* npeaks);
+/* ... after Localization: 0 copies them; 1 fits, and keeps those with |fitted value| >
+ * keep_threshold (float against float), in candidate order.  out: host or device memory. */
+int spim_detect_interest_points(const float* img, const int64_t* dims, float min_peak, int32_t find_min,
+                                int32_t find_max, int32_t ij_threads, int32_t route, int32_t device,
+                                int32_t localization, float keep_threshold, spim_interest_point* out,
+                                int64_t max_out, int64_t* nout);
+/* The stage's tile sizes, from the constants in the code (for tests that aim at its seams):
+ * columns tested per wave, rows per lane, centre planes per chunk, entries of a wave's
+ * candidate buffer, the least capacity of the candidate lists.  Host only: needs no GPU. */
+void spim_detect_tiles(int32_t sizes[5]);
+
+/* ======================================================================
  * 6b'. Downsampling in front of the detectors ("Downsample_XY" / "Downsample_Z") --
  *     spim/process/interestpointdetection/Downsample.java:65-162 (simple2x along one axis),
  *     spim/fiji/plugin/interestpointdetection/DifferenceOf.java:446-535 (openAndDownsample:

@@ -193,7 +193,7 @@ def dog_image(img_norm: np.ndarray, sigma: float, image_sigma=(0.5, 0.5, 0.5)) -
 def find_peaks(dog: np.ndarray, min_value: float, ij_threads: int = 8):
     """mpicbg/spim/segmentation/InteractiveIntegral.java:360-468.
 
-    Skips the 1-voxel border; |v| >= min_value; 26-neighbour test with
+    Skips the 1-voxel border and |v| < min_value; 26-neighbour test with
     inclusive comparisons; "all neighbours >= centre" => MAX (bright bead),
     "all <= centre" => MIN.  Returned order = the reference's: per-thread
     lists by ``x % T`` concatenated, each in flat (x-fastest) order.
@@ -213,7 +213,10 @@ def find_peaks(dog: np.ndarray, min_value: float, ij_threads: int = 8):
                 nb = d[1 + dz:nz - 1 + dz, 1 + dy:ny - 1 + dy, 1 + dx:nx - 1 + dx]
                 ge &= nb >= c
                 le &= nb <= c
-    cand = np.abs(c) >= np.float32(min_value)
+    # "if ( Math.abs( currentValue ) < minValue ) continue" (:409), literally: a NaN
+    # minValue skips nothing (a NaN voxel fails every comparison below)
+    with np.errstate(invalid="ignore"):
+        cand = ~(np.abs(c) < np.float32(min_value))
     is_max = cand & ge
     is_min = cand & le & ~ge
     zz, yy, xx = np.nonzero(is_max | is_min)

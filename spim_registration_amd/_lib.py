@@ -223,6 +223,11 @@ SIGNATURES = {
     "spim_dom_compute": (C.c_int, [_pf, _pi64, C.POINTER(DomParams), _pf, C.POINTER(Peak), _i64, _pi64]),
     "spim_dom_interest_points": (C.c_int, [_pf, _pi64, C.POINTER(DomParams), _pf,
                                            C.POINTER(InterestPointC), _i64, _pi64]),
+    "spim_detect_peaks": (C.c_int, [C.c_void_p, _pi64, _f32, _i32, _i32, _i32, _i32, _i32, C.POINTER(Peak), _i64,
+                                    _pi64]),
+    "spim_detect_interest_points": (C.c_int, [C.c_void_p, _pi64, _f32, _i32, _i32, _i32, _i32, _i32, _i32, _f32,
+                                              C.POINTER(InterestPointC), _i64, _pi64]),
+    "spim_detect_tiles": (None, [C.POINTER(_i32)]),
     "spim_downsample_dims": (C.c_int, [_pi64, C.POINTER(_i32), _pi64]),
     "spim_downsample": (C.c_int, [C.c_void_p, _pi64, C.POINTER(_i32), C.c_int, C.c_void_p]),
     "spim_downsample_factor_xy": (C.c_int, [C.c_int, _i32, _pd, C.POINTER(_i32)]),

@@ -56,7 +56,9 @@ __device__ __forceinline__ void sink_append(const PeakSink& pk, bool flag, int x
 // vs 0.42 ms per 768^3).  A centre plane next to a plane holding a NaN
 // (any loaded value of the wave) takes the reference's comparison loop over the image
 // for the wave (NaN compares false; min3 / max3 would drop it).
+constexpr int kDpkX = 62;   // columns tested per wave (lanes 1 .. 62)
 constexpr int kDpkY = 4;    // rows per lane
+constexpr int kDpkZ = 64;   // centre planes per chunk
 constexpr int kDpkPD = 2;   // planes loaded ahead
 __device__ __forceinline__ float dpp_from_left(float v) {    // lane i <- lane i - 1 (wave_shr:1)
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, false));
@@ -73,7 +75,7 @@ __global__ __launch_bounds__(256) void k_dog_peaks(Dims3 d, const float* __restr
     __shared__ int4 cbuf[4][kCandBuf];
     const int lane = int(threadIdx.x & 63), wv = int(threadIdx.x >> 6);
     const int nx = int(d.nx), ny = int(d.ny), nz = int(d.nz);
-    const int nsx = (nx - 2 + 61) / 62, nyb = (ny - 2 + DPY - 1) / DPY;
+    const int nsx = (nx - 2 + kDpkX - 1) / kDpkX, nyb = (ny - 2 + DPY - 1) / DPY;
     const int nzc = (nz - 2 + zc_len - 1) / zc_len;
     // xcd: blocks go round-robin to the 8 XCDs; the logical block index gives each XCD a
     // contiguous range, so the y-neighbour waves sharing a halo row run on one L2
@@ -85,8 +87,8 @@ __global__ __launch_bounds__(256) void k_dog_peaks(Dims3 d, const float* __restr
     const int wid = __builtin_amdgcn_readfirstlane(lb * 4 + wv);
     if (wid >= nsx * nyb * nzc) return;   // (wave-uniform; no block barriers below)
     const int sx = wid % nsx, yb = (wid / nsx) % nyb, zb = wid / (nsx * nyb);
-    const int x = sx * 62 + lane;                       // lane 0: the halo column x0 - 1
-    const bool xt = lane >= 1 && lane <= 62 && x <= nx - 2;
+    const int x = sx * kDpkX + lane;                       // lane 0: the halo column x0 - 1
+    const bool xt = lane >= 1 && lane <= kDpkX && x <= nx - 2;
     const int xl = min(x, nx - 1);
     const int ybase = yb * DPY;                         // row r of the lane: y = ybase + r (r = 0: halo)
     const int tlo = 1 + zb * zc_len, thi = min(nz - 1, tlo + zc_len);   // centre planes tested
@@ -362,8 +364,8 @@ void stored_candidates(DogWork& w, const Dims3& d, const float* dogp, bool peaks
         SD_HIP(hipMemcpyAsync(w.sink.p, &pk, sizeof(pk), hipMemcpyHostToDevice, s));   // (synchronised by the caller)
         const int want = pk.want_min | (pk.want_max << 1);
         if (d.nx >= 3 && d.ny >= 3 && d.nz >= 3) {   // (else no voxel has 26 neighbours)
-            constexpr int zcp = 64;
-            const int64_t nwave = ceil_div(d.nx - 2, int64_t(62)) * ceil_div(d.ny - 2, int64_t(kDpkY)) *
+            constexpr int zcp = kDpkZ;
+            const int64_t nwave = ceil_div(d.nx - 2, int64_t(kDpkX)) * ceil_div(d.ny - 2, int64_t(kDpkY)) *
                                   ceil_div(d.nz - 2, int64_t(zcp));
             const dim3 gp(unsigned(ceil_div(nwave, int64_t(4))));
             hipLaunchKernelGGL((k_dog_peaks<kDpkY, kDpkPD>), gp, dim3(256), 0, s, d, dogp, zcp, pk.minv, want, w.sink.p, 1);
@@ -392,8 +394,9 @@ void sort_candidates(DogWork& w, unsigned total, int T, hipStream_t s, DogRun& r
 }
 
 void detect_stored(DogWork& w, const Dims3& d, const float* img, float min_peak, int want_min, int want_max, int T,
-                   hipStream_t s, DogRun& r) {
-    const bool pkk = image_below_4gib(d.nx * d.ny * d.nz);   // (k_dog_peaks' one buffer resource)
+                   hipStream_t s, DogRun& r, int route) {
+    // (k_dog_peaks' one buffer resource; the route is checked by the caller)
+    const bool pkk = route == SPIM_DETECT_ROUTE_APPEND ? false : image_below_4gib(d.nx * d.ny * d.nz);
     const unsigned total = collect_candidates(w, d.nx * d.ny * d.nz, min_peak, want_min, want_max, T, s,
                                               [&](const PeakSink& pk, int) { stored_candidates(w, d, img, pkk, pk, s); });
     r.d = d;
@@ -476,6 +479,58 @@ void points_from_peaks(DogWork& w, const DogRun& r, int localization, float keep
     *nout = n;
 }
 
+// ---------------------------------------------------------------- the stage on a caller's image
+namespace {
+
+struct DetectArgs {   // (what check_detector_args reads of a detector's parameters)
+    int localization, ij_threads;
+};
+
+// the caller's image staged (or read in place) and its candidates, for both entries
+void detect_run(const float* img, const int64_t* dims, float min_peak, int find_min, int find_max, int T, int route,
+                int device, hipStream_t s, DogWork& w, DogRun& r) {
+    const Dims3 d{dims[0], dims[1], dims[2]};
+    const float* in = stage_view(w, img, d.nx * d.ny * d.nz, device, s);
+    detect_stored(w, d, in, min_peak, find_min ? 1 : 0, find_max ? 1 : 0, T, s, r, route);
+}
+
+void detect_check(const float* img, const int64_t* dims, const DetectArgs& a, int route) {
+    check_detector_args(img, dims, &a, [&] {
+        SD_CHECK(dims[0] < (int64_t(1) << 31) && dims[1] < (int64_t(1) << 31) && dims[2] < (int64_t(1) << 31) &&
+                     dims[0] * dims[1] < (int64_t(1) << 31) && dims[0] * dims[1] * dims[2] < (int64_t(1) << 40),
+                 SPIMDECON_ERR_ARG, "volume too large");
+        SD_CHECK(route == SPIM_DETECT_ROUTE_AUTO || route == SPIM_DETECT_ROUTE_WAVE || route == SPIM_DETECT_ROUTE_APPEND,
+                 SPIMDECON_ERR_ARG, "route must be SPIM_DETECT_ROUTE_AUTO (0), _WAVE (1) or _APPEND (2)");
+        SD_CHECK(route != SPIM_DETECT_ROUTE_WAVE || image_below_4gib(dims[0] * dims[1] * dims[2]), SPIMDECON_ERR_ARG,
+                 "SPIM_DETECT_ROUTE_WAVE needs an image below 4 GiB");
+    });
+}
+
+}  // namespace
+
+void detect_peaks(const float* img, const int64_t* dims, float min_peak, int find_min, int find_max, int T, int route,
+                  int device, spim_peak* peaks, int64_t max_peaks, int64_t* npeaks) {
+    SD_CHECK(npeaks, SPIMDECON_ERR_ARG, "null argument");
+    detect_check(img, dims, DetectArgs{0, T}, route);
+    with_detector(device, [&](DogWork& w, hipStream_t s) {
+        DogRun r;
+        detect_run(img, dims, min_peak, find_min, find_max, T, route, device, s, w, r);
+        peaks_to_host(r, peaks, max_peaks, npeaks, s);
+    });
+}
+
+void detect_interest_points(const float* img, const int64_t* dims, float min_peak, int find_min, int find_max, int T,
+                            int route, int device, int localization, float keep_thr, spim_interest_point* out,
+                            int64_t max_out, int64_t* nout) {
+    SD_CHECK(nout, SPIMDECON_ERR_ARG, "null argument");
+    detect_check(img, dims, DetectArgs{localization, T}, route);
+    with_detector(device, [&](DogWork& w, hipStream_t s) {
+        DogRun r;
+        detect_run(img, dims, min_peak, find_min, find_max, T, route, device, s, w, r);
+        points_from_peaks(w, r, localization, keep_thr, out, max_out, nout, s);
+    });
+}
+
 void dog_release_workspace(int dev) {
     with_workspace(dev, [](DogWork& w) {
         SD_HIP(hipDeviceSynchronize());
@@ -487,4 +542,33 @@ void dog_release_workspace(int dev) {
 
 extern "C" int spim_dog_release_workspace(int device) {
     return spimdecon::guarded([&] { spimdecon::dog_release_workspace(device); });
+}
+
+extern "C" int spim_detect_peaks(const float* img, const int64_t* dims, float min_peak, int32_t find_min,
+                                 int32_t find_max, int32_t ij_threads, int32_t route, int32_t device,
+                                 spim_peak* peaks, int64_t max_peaks, int64_t* npeaks) {
+    return spimdecon::guarded([&] {
+        spimdecon::detect_peaks(img, dims, min_peak, find_min, find_max, ij_threads, route, device, peaks, max_peaks,
+                                npeaks);
+    });
+}
+
+extern "C" int spim_detect_interest_points(const float* img, const int64_t* dims, float min_peak, int32_t find_min,
+                                           int32_t find_max, int32_t ij_threads, int32_t route, int32_t device,
+                                           int32_t localization, float keep_threshold, spim_interest_point* out,
+                                           int64_t max_out, int64_t* nout) {
+    return spimdecon::guarded([&] {
+        spimdecon::detect_interest_points(img, dims, min_peak, find_min, find_max, ij_threads, route, device,
+                                          localization, keep_threshold, out, max_out, nout);
+    });
+}
+
+extern "C" void spim_detect_tiles(int32_t sizes[5]) {
+    using namespace spimdecon;
+    if (!sizes) return;
+    sizes[0] = kDpkX;
+    sizes[1] = kDpkY;
+    sizes[2] = kDpkZ;
+    sizes[3] = kCandBuf;
+    sizes[4] = int32_t(kCandCapFloor);
 }

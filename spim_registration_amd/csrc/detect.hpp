@@ -142,13 +142,16 @@ struct DogRun {
     const PeakOut* dpeaks = nullptr;
 };
 
+// the least capacity of the candidate lists (collect_candidates)
+constexpr int64_t kCandCapFloor = int64_t(1) << 16;
+
 // The candidate pass of a detector: `launch(pk, attempt)` enqueues the kernel(s) that append
 // to the sink pk; a count beyond the capacity reruns it once with room for every candidate.
 template <typename Launch>
 unsigned collect_candidates(DogWork& w, int64_t n, float min_peak, int wmin, int wmax, int T, hipStream_t s,
                             Launch&& launch) {
     grow(w.count, 1);
-    unsigned cap = unsigned(std::min<int64_t>(std::max<int64_t>(int64_t(1) << 16, n / 256), int64_t(1) << 30));
+    unsigned cap = unsigned(std::min<int64_t>(std::max<int64_t>(kCandCapFloor, n / 256), int64_t(1) << 30));
     cap = std::max<unsigned>(cap, unsigned(std::min<size_t>(w.recs.n, size_t(1) << 30)));
     unsigned total = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -176,9 +179,10 @@ void sort_candidates(DogWork& w, unsigned total, int T, hipStream_t s, DogRun& r
 
 // InteractiveIntegral.findPeaks over a stored device image: the extrema with
 // |v| >= min_peak of the wanted kinds, in the reference's order, into r.np / r.dpeaks
-// (the workspace's memory).  Synchronises the stream.
+// (the workspace's memory).  Synchronises the stream.  route: SPIM_DETECT_ROUTE_* (AUTO:
+// k_dog_peaks where the image lies below 4 GiB, else k_peaks_append).
 void detect_stored(DogWork& w, const Dims3& d, const float* img, float min_peak, int want_min, int want_max, int T,
-                   hipStream_t s, DogRun& r);
+                   hipStream_t s, DogRun& r, int route = SPIM_DETECT_ROUTE_AUTO);
 
 // the first min(r.np, max_peaks) candidates to the host; *npeaks = r.np
 void peaks_to_host(const DogRun& r, spim_peak* peaks, int64_t max_peaks, int64_t* npeaks, hipStream_t s);

@@ -224,3 +224,55 @@ def process_dom(img, radius1=2, radius2=3, threshold=0.02, localization=0, image
         pts = [(float(x), float(y), float(z), float(v)) for x, y, z, v in dog_ref.quadratic_localization(dom, pts)
                if abs(v) > np.float32(threshold)]
     return pts, peaks, dom
+
+
+# ------------------------------------------------------------------ k_dom's z chunks
+def z_chunks(nz, hm_z):
+    """csrc/dom.hip, dom_tile's rule restated: a block walks max(64, 8 hm_z) output planes of
+    the nz - 2 hm_z that the boxes reach, and starts its running z sums afresh.  Returns the
+    chunks' lengths."""
+    zc, inner = max(64, 8 * hm_z), nz - 2 * hm_z
+    return [min(zc, inner - z0) for z0 in range(0, max(inner, 0), zc)]
+
+
+def tile_columns(hm):
+    """dom_tile's choice restated: among tiles of 16 / 32 / 64 x 1 .. 32 outputs whose columns
+    (tile + halo) number at most 16 x 256 and whose two LDS tiles of 16-byte entries fit 64 KiB,
+    the first with the highest outputs per column x min(blocks per 160 KiB, 4).  Returns its
+    columns: more than 8 x 256 take the instantiation of 16 columns per thread."""
+    best, ncol_best = -1.0, 0
+    for lx in (4, 5, 6):
+        for ty in range(1, 33):
+            tx, hx, hy = 1 << lx, (1 << lx) + 2 * hm[0], ty + 2 * hm[1]
+            ncol, lds = hx * hy, (hx * hy + tx * hy) * 16
+            if ncol > 16 * 256 or lds > 64 * 1024:
+                continue
+            score = tx * ty / ncol * min(160 * 1024 // lds, 4)
+            if score > best:
+                best, ncol_best = score, ncol
+    return ncol_best
+
+
+# name -> ((nz, ny, nx), keywords of process_dom, the chunks' lengths)
+Z_CHUNK_CASES = {
+    "ragged": ((64 + 6 + 5, 20, 24), {}, [64, 5]),
+    "two_full": ((2 * 64 + 6, 20, 24), {}, [64, 64]),
+    "largest_box": ((128 + 32 + 3, 36, 40), {"radius1": 15, "radius2": 16}, [128, 3]),     # 16 columns per thread
+    "anisotropic": ((96 + 24 + 5, 14, 20), {"image_sigma": (0.5, 0.5, 0.125)}, [96, 5]),   # hm_z 12, hm_x 3
+}
+
+
+def z_chunk_volume(name):
+    shape = Z_CHUNK_CASES[name][0]
+    img = (np.random.default_rng(len(name)).random(shape) * 4000).astype(np.float32)
+    img.setflags(write=False)
+    return img
+
+
+def sparse_integer_volume(shape=(75, 20, 24), seed=17):
+    """Zeros with a few small integers: the box sums tie over wide regions (plateaus of equal
+    DOM values, exact zeros among them), across the chunk seam too."""
+    rng = np.random.default_rng(seed)
+    img = np.where(rng.random(shape) < 0.004, np.round(rng.random(shape) * 5) + 1, 0).astype(np.float32)
+    img.setflags(write=False)
+    return img

@@ -190,3 +190,30 @@ def test_golden_equals_the_restatement():
     assert [(p[0], p[1], p[2], int(p[4]), int(p[5])) for p in peaks] == [tuple(r) for r in g["peaks"].tolist()]
     np.testing.assert_array_equal(np.float32([p[3] for p in peaks]), g["intensity"])
     assert g["peaks"][:, 4].sum() > 0 and g["peaks"][:, 3].sum() > 0     # maxima and minima
+
+
+@pytest.mark.parametrize("name", list(dr.Z_CHUNK_CASES))
+def test_z_chunk_cases_start_a_second_chunk(name):
+    """The shapes of tests/test_gpu_dom.py::test_dom_across_z_chunks, from dom_tile's rule
+    restated (dom_ref.z_chunks): two chunks each, ragged or full as the name says."""
+    shape, kw, chunks = dr.Z_CHUNK_CASES[name]
+    s1, s2 = dr.box_diameters(kw.get("radius1", 2), kw.get("radius2", 3), kw.get("image_sigma", (0.5, 0.5, 0.5)))
+    hm = [max(a, b) // 2 for a, b in zip(s1, s2)]
+    assert dr.z_chunks(shape[0], hm[2]) == chunks and len(chunks) == 2
+    assert all(n > 2 * h for n, h in zip(shape[::-1], hm)) and np.prod(shape) < 250_000
+    if name == "anisotropic":
+        assert hm[2] != hm[0] and 8 * hm[2] > 64
+    if name == "largest_box":
+        assert dr.tile_columns(hm) > 8 * 256 >= dr.tile_columns([3, 3, 3])      # 16 columns per thread
+
+
+def test_sparse_integers_tie_across_the_chunk_seam():
+    img = dr.sparse_integer_volume()
+    pts, peaks, d = dr.process_dom(img, threshold=0.0, find_min=True, find_max=True)
+    assert dr.z_chunks(img.shape[0], 3) == [64, 5]
+    seam = 3 + 64                                   # the first output plane of the second chunk
+    inner = d[3:-3, 3:-3, 3:-3]
+    assert np.unique(inner).size < inner.size // 20      # ties
+    # plateau voxels (every neighbour equal) are candidates, on both sides of the seam
+    flat = {p[:3] for p in peaks if np.all(d[p[2] - 1:p[2] + 2, p[1] - 1:p[1] + 2, p[0] - 1:p[0] + 2] == d[p[2], p[1], p[0]])}
+    assert {z for _, _, z in flat} >= {seam - 1, seam} and all(p[5] for p in peaks if p[:3] in flat)

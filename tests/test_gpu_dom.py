@@ -176,6 +176,29 @@ def test_dom_edge_shapes(gpu, shape, kw):
     assert (np.count_nonzero(d) > 0) == fits
 
 
+@pytest.mark.parametrize("name", list(dr.Z_CHUNK_CASES))
+def test_dom_across_z_chunks(gpu, name):
+    """More output planes than one block walks (max(64, 8 hm_z)): the running z sums start
+    afresh at the second chunk -- ragged and full last chunks, the 128-plane chunk of the
+    largest box (16 columns per thread), and a 96-plane chunk with hm_z != hm_x."""
+    shape, kw, chunks = dr.Z_CHUNK_CASES[name]
+    img = dr.z_chunk_volume(name)
+    for dev in (False, True):
+        peaks = check(img, device_tensor=dev, threshold=0.001, find_min=True, **kw)
+    hm_z = (shape[0] - sum(chunks)) // 2
+    assert {p[2] for p in peaks} >= {hm_z + chunks[0] - 1, hm_z + chunks[0]} or name == "largest_box"
+    assert len(peaks) > 0
+
+
+def test_dom_integer_plateaus_across_z_chunks(gpu):
+    """Sparse small integers: box sums tie, whole regions share one DOM value; >= and <= and
+    the MAX-first rule decide, on both sides of the chunk seam."""
+    img = dr.sparse_integer_volume()
+    for dev in (False, True):
+        peaks = check(img, device_tensor=dev, threshold=0.0, find_min=True, find_max=True)
+    assert len(peaks) > 1000
+
+
 def test_dom_constant_image(gpu):
     """diff = 0: NaN where the boxes fit, the zero frame around it, no peaks."""
     for value in (0.0, 7.0, -3.5):
