@@ -8,7 +8,7 @@
 //
 // The maximal box is fused at the dialog's downsampling (nearest neighbour, no blending: the
 // existing fusion kernel, into device memory), then
-//   min / max      Math.min / Math.max from +-Float.MAX_VALUE           k_mm_partial, k_mm_final
+//   min / max      Math.min / Math.max from +-Float.MAX_VALUE   k_minmax_partial, k_minmax_final
 //   threshold      double(float(max - min)) * (background / 100.0) + double(min)            (host)
 //   minimum filter x, then y, then z; window 2r + 1 over a zero extension; Math.min
 //                  from Float.MAX_VALUE                                  k_minfilter<axis>
@@ -31,15 +31,11 @@
 #include <cmath>
 #include <cstring>
 
-#include "common.hpp"
+#include "fusion.hpp"
+#include "hostcall.hpp"
+#include "minmax.hpp"
 
 namespace spimdecon {
-
-// input_prep.hip
-void fuse_weighted_average(int nviews, const spim_view_source* views, const spim_fusion_params* p,
-                           const float* borders, const float* ranges, const double* sigma1, const double* sigma2,
-                           float* out);
-
 namespace {
 
 constexpr int kMfLines = 64;            // lines per block = lanes of its one wave
@@ -47,8 +43,6 @@ constexpr int kMfTileSmall = 64;        // outputs per line and block, r <= kMfS
 constexpr int kMfTileLarge = 128;       // ... above it (the halo of 2r is shared by more outputs)
 constexpr int kMfSmallRadius = 16;
 constexpr int kMfMaxRadius = SPIM_MIN_FILTER_MAX_RADIUS;
-constexpr int kRedBlock = 256, kRedGrid = 1024;
-constexpr float kFloatMax = 3.402823466e+38f;
 
 static_assert((kMfTileLarge + 2 * kMfMaxRadius) * (kMfLines + 1) * 4 <= 160 * 1024, "LDS of one block");
 
@@ -66,55 +60,10 @@ __device__ __forceinline__ float jmax(float a, float b) {
     return m;
 }
 
-// ---------------------------------------------------------------- min / max
-__device__ __forceinline__ void block_minmax(float& mn, float& mx) {
-    __shared__ float smn[kRedBlock / 64], smx[kRedBlock / 64];
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = jmin(mn, __shfl_xor(mn, off, 64));
-        mx = jmax(mx, __shfl_xor(mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        smn[threadIdx.x >> 6] = mn;
-        smx[threadIdx.x >> 6] = mx;
-    }
-    __syncthreads();
-    mn = smn[0];
-    mx = smx[0];
-    for (int w = 1; w < kRedBlock / 64; ++w) {
-        mn = jmin(mn, smn[w]);
-        mx = jmax(mx, smx[w]);
-    }
-}
-
-// a fixed tree (grid-stride partials, then one block): the result does not depend on scheduling
-__global__ __launch_bounds__(kRedBlock) void k_mm_partial(const float* __restrict__ c, int64_t n,
-                                                          float* __restrict__ part) {
-    float mn = kFloatMax, mx = -kFloatMax;
-    for (int64_t i = int64_t(blockIdx.x) * kRedBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kRedBlock) {
-        const float v = c[i];
-        mn = jmin(mn, v);
-        mx = jmax(mx, v);
-    }
-    block_minmax(mn, mx);
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = mn;
-        part[2 * blockIdx.x + 1] = mx;
-    }
-}
-
-__global__ __launch_bounds__(kRedBlock) void k_mm_final(const float* __restrict__ part, int nparts,
-                                                        float* __restrict__ mm) {
-    float mn = kFloatMax, mx = -kFloatMax;
-    for (int i = threadIdx.x; i < nparts; i += kRedBlock) {
-        mn = jmin(mn, part[2 * i]);
-        mx = jmax(mx, part[2 * i + 1]);
-    }
-    block_minmax(mn, mx);
-    if (threadIdx.x == 0) {
-        mm[0] = mn;
-        mm[1] = mx;
-    }
-}
+struct BoxMinMax {   // the rule of minmax.hpp's reduction
+    static __device__ __forceinline__ float mn(float a, float b) { return jmin(a, b); }
+    static __device__ __forceinline__ float mx(float a, float b) { return jmax(a, b); }
+};
 
 // ---------------------------------------------------------------- the box of voxels above a threshold
 // box: min x, y, z (start: the dims), max x, y, z (start: 0).  A lane's box, reduced over its
@@ -271,44 +220,21 @@ __global__ __launch_bounds__(kMfLines) void k_minfilter(const float* __restrict_
 }
 
 // ---------------------------------------------------------------- host side
-struct BoxWork {
-    std::mutex mu;
+struct BoxWork : WorkBase {
     DBuf<float> t1, t2, fused, red;
     DBuf<int> box;
-    hipStream_t stream = nullptr;
-    hipStream_t get_stream() {
-        if (!stream) SD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        return stream;
-    }
     void release() {
-        if (stream) {
-            (void)hipStreamDestroy(stream);
-            stream = nullptr;
-        }
-        t1.release();
-        t2.release();
-        fused.release();
-        red.release();
-        box.release();
+        release_stream();
+        release_all(t1, t2, fused, red, box);
     }
 };
 
-template <typename Body>
-void with_box_work(int device, Body&& body) {
-    check_device(device);
-    DeviceGuard guard(device);
-    BoxWork& w = per_device<BoxWork>(device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    body(w, w.get_stream());
-}
-
 int64_t check_image(const float* img, const int64_t* dims) {
     SD_CHECK(img && dims, SPIMDECON_ERR_ARG, "null argument");
-    SD_CHECK(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1, SPIMDECON_ERR_ARG, "bad dims");
-    SD_CHECK(dims[0] < (int64_t(1) << 30) && dims[1] < (int64_t(1) << 30) && dims[2] < (int64_t(1) << 30) &&
-                 dims[0] * dims[1] < (int64_t(1) << 31) && dims[0] * dims[1] * dims[2] < (int64_t(1) << 40),
-             SPIMDECON_ERR_ARG, "volume too large");
-    return dims[0] * dims[1] * dims[2];
+    const int64_t n = check_volume(dims, "bad dims", "volume too large");
+    SD_CHECK(dims[0] * dims[1] < (int64_t(1) << 31) && n < (int64_t(1) << 40), SPIMDECON_ERR_ARG,
+             "volume too large");
+    return n;
 }
 
 void check_radius(int radius) {
@@ -322,20 +248,10 @@ void check_background(double background) {
              "background must lie inside (0, 100) percent");
 }
 
-// the image on the device: itself, or one upload into `stage`
-const float* stage_in(const float* img, int64_t n, int device, DBuf<float>& stage, hipStream_t s) {
-    if (is_device_ptr(img, device)) return img;
-    grow(stage, size_t(n));
-    SD_HIP(hipMemcpyAsync(stage.p, img, size_t(n) * 4, hipMemcpyDefault, s));
-    return stage.p;
-}
-
 void minmax_device(BoxWork& w, const float* dimg, int64_t n, float* mn, float* mx, hipStream_t s) {
-    const int parts = int(std::max<int64_t>(1, std::min<int64_t>(kRedGrid, ceil_div(n, kRedBlock))));
     grow(w.red, size_t(2 * kRedGrid + 2));
     float* mm = w.red.p + 2 * kRedGrid;
-    hipLaunchKernelGGL(k_mm_partial, dim3(unsigned(parts)), dim3(kRedBlock), 0, s, dimg, n, w.red.p);
-    hipLaunchKernelGGL(k_mm_final, dim3(1), dim3(kRedBlock), 0, s, w.red.p, parts, mm);
+    minmax_launch<BoxMinMax>(dimg, n, minmax_parts(n), w.red.p, mm, s);
     SD_HIP(hipGetLastError());
     float h[2];
     SD_HIP(hipMemcpyAsync(h, mm, sizeof(h), hipMemcpyDeviceToHost, s));
@@ -414,7 +330,7 @@ void filter_device(BoxWork& w, const float* in, const int64_t* dims, int r, floa
 void min_max(const float* img, const int64_t* dims, int device, float* mn, float* mx) {
     SD_CHECK(mn && mx, SPIMDECON_ERR_ARG, "null argument");
     const int64_t n = check_image(img, dims);
-    with_box_work(device, [&](BoxWork& w, hipStream_t s) {
+    with_work<BoxWork>(device, [&](BoxWork& w, hipStream_t s) {
         minmax_device(w, stage_in(img, n, device, w.t2, s), n, mn, mx, s);
     });
 }
@@ -423,13 +339,11 @@ void min_filter(const float* img, const int64_t* dims, int radius, int device, f
     SD_CHECK(out, SPIMDECON_ERR_ARG, "null argument");
     const int64_t n = check_image(img, dims);
     check_radius(radius);
-    with_box_work(device, [&](BoxWork& w, hipStream_t s) {
-        grow(w.t1, size_t(n));
-        grow(w.t2, size_t(n));     // (before staging into it: growing does not keep the contents)
+    with_work<BoxWork>(device, [&](BoxWork& w, hipStream_t s) {
         const float* in = stage_in(img, n, device, w.t2, s);
-        const bool out_dev = is_device_ptr(out, device);
-        filter_device(w, in, dims, radius, out_dev ? out : w.t1.p, false, 0.0, s);
-        if (!out_dev) SD_HIP(hipMemcpyAsync(out, w.t1.p, size_t(n) * 4, hipMemcpyDefault, s));
+        ImageDest dst(out, n, device);
+        filter_device(w, in, dims, radius, dst.store(w.t1), false, 0.0, s);
+        dst.copy_out(s);
         SD_HIP(hipStreamSynchronize(s));
     });
 }
@@ -439,7 +353,7 @@ void threshold_bounds(const float* img, const int64_t* dims, double threshold, i
     SD_CHECK(bmin && bmax && found, SPIMDECON_ERR_ARG, "null argument");
     const int64_t n = check_image(img, dims);
     SD_CHECK(!std::isnan(threshold), SPIMDECON_ERR_ARG, "threshold is NaN");
-    with_box_work(device, [&](BoxWork& w, hipStream_t s) {
+    with_work<BoxWork>(device, [&](BoxWork& w, hipStream_t s) {
         const float* in = stage_in(img, n, device, w.t2, s);
         box_reset(w, dims, s);
         const unsigned grid = unsigned(std::max<int64_t>(1, std::min<int64_t>(2048, ceil_div(n, kRedBlock))));
@@ -458,12 +372,10 @@ void segment_device(BoxWork& w, const float* dimg, const int64_t* dims, double b
     minmax_device(w, dimg, n, &res->min, &res->max, s);
     res->threshold = threshold_of(res->min, res->max, background);
     box_reset(w, dims, s);
-    const bool f_dev = filtered && is_device_ptr(filtered, device);
     // a host `filtered` is written through t1 (free once the y pass has read it)
-    grow(w.t1, size_t(n));
-    float* dst = !filtered ? nullptr : f_dev ? filtered : w.t1.p;
-    filter_device(w, dimg, dims, radius, dst, true, res->threshold, s);
-    if (filtered && !f_dev) SD_HIP(hipMemcpyAsync(filtered, w.t1.p, size_t(n) * 4, hipMemcpyDefault, s));
+    ImageDest dst(filtered, n, device);
+    filter_device(w, dimg, dims, radius, filtered ? dst.store(w.t1) : nullptr, true, res->threshold, s);
+    dst.copy_out(s);
     box_fetch(w, res->bounds_min, res->bounds_max, &res->found, s);
 }
 
@@ -473,8 +385,7 @@ void segment_bounds(const float* img, const int64_t* dims, double background, in
     const int64_t n = check_image(img, dims);
     check_radius(radius);
     check_background(background);
-    with_box_work(device, [&](BoxWork& w, hipStream_t s) {
-        grow(w.t2, size_t(n));
+    with_work<BoxWork>(device, [&](BoxWork& w, hipStream_t s) {
         const float* in = stage_in(img, n, device, w.t2, s);
         segment_device(w, in, dims, background, radius, filtered, device, res, s);
     });
@@ -537,7 +448,7 @@ void auto_bounding_box(int nviews, const spim_view_source* views, const spim_aut
     SD_CHECK(res->fused_dims[0] >= 1 && res->fused_dims[1] >= 1 && res->fused_dims[2] >= 1, SPIMDECON_ERR_ARG,
              "downsampling leaves no voxel of the maximal bounding box");
     const int64_t n = check_image(views[0].img, res->fused_dims);
-    with_box_work(p->device, [&](BoxWork& w, hipStream_t s) {
+    with_work<BoxWork>(p->device, [&](BoxWork& w, hipStream_t s) {
         grow(w.fused, size_t(n));
         spim_fusion_params fp;
         spim_fusion_params_default(&fp);
@@ -561,16 +472,6 @@ void auto_bounding_box(int nviews, const spim_view_source* views, const spim_aut
         res->bb_max[a] = res->seg.bounds_max[a] * p->downsampling + res->max_min[a] + 3 * int64_t(res->radius_min);
         res->bb_dims[a] = res->bb_max[a] - res->bb_min[a] + 1;
     }
-}
-
-void release_box_work(int device) {
-    SD_CHECK(device >= 0, SPIMDECON_ERR_ARG, "bad device");
-    PerDevice<BoxWork> all = per_device_all<BoxWork>();
-    auto it = all.by_dev.find(device);
-    if (it == all.by_dev.end() || !it->second) return;
-    DeviceGuard guard(device);
-    std::lock_guard<std::mutex> lk(it->second->mu);
-    it->second->release();
 }
 
 }  // namespace
@@ -617,5 +518,5 @@ extern "C" int spim_auto_bounding_box(int nviews, const spim_view_source* views,
 }
 
 extern "C" int spim_bbox_release_workspace(int device) {
-    return guarded([&] { release_box_work(device); });
+    return guarded([&] { release_work<BoxWork>(device); });
 }

@@ -16,10 +16,6 @@ thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 void clear_last_error() { g_last_error.clear(); }
 
-void fft_convolve_block(float* im, const int* imDim, const float* kernel, const int* kernelDim,
-                        int dev, float* out);
-void slab_range(int64_t nz, int nparts, int idx, int64_t* z0, int64_t* z1);
-
 }  // namespace spimdecon
 
 using namespace spimdecon;

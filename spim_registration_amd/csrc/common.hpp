@@ -50,6 +50,9 @@ void check_device(int dev);
 // true when p is device memory of `dev` itself
 bool is_device_ptr(const void* p, int dev);
 
+// In-place circular convolution of one block (see spimdecon.h; legacy.cpp)
+void fft_convolve_block(float* im, const int* imDim, const float* kernel, const int* kernelDim, int dev, float* out);
+
 // Scoped hipSetDevice with restore.
 struct DeviceGuard {
     int prev = -1;

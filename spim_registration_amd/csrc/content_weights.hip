@@ -23,13 +23,12 @@
 #include <cmath>
 #include <vector>
 
-#include "common.hpp"
+#include "fusion.hpp"
+#include "hostcall.hpp"
+#include "minmax.hpp"
 #include "resample.hpp"
-#include "spimdecon.h"
 
 namespace spimdecon {
-void check_device(int dev);
-
 namespace {
 
 constexpr int kCwBlock = 512;                   // 8 waves: one group of outputs each
@@ -38,7 +37,6 @@ constexpr int kCwOut = 16;                      // outputs per thread along the 
 constexpr int kCwTile = kCwOut * (kCwBlock / 64);  // 128 outputs per line and block
 constexpr int kCwChunk = 16;                    // taps per register-window step
 constexpr int kCwMaxTaps = 463;                 // LDS: 64 x ((128 + 464) | 1) floats <= 160 KiB
-constexpr int kRedBlock = 256, kRedGrid = 1024;
 
 inline int padded_taps(int k) { return (k + kCwChunk - 1) / kCwChunk * kCwChunk; }
 inline int lds_width(int k) { return kCwTile + padded_taps(k); }
@@ -179,53 +177,10 @@ __global__ __launch_bounds__(kCwBlock) void k_gauss_pass(const float* __restrict
 __device__ __forceinline__ float jmin(float a, float b) { return a != a ? a : (b != b ? b : fminf(a, b)); }
 __device__ __forceinline__ float jmax(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
 
-__device__ __forceinline__ void block_minmax(float& mn, float& mx) {
-    __shared__ float smn[kRedBlock / 64], smx[kRedBlock / 64];
-    for (int off = 32; off > 0; off >>= 1) {
-        mn = jmin(mn, __shfl_xor(mn, off, 64));
-        mx = jmax(mx, __shfl_xor(mx, off, 64));
-    }
-    if ((threadIdx.x & 63) == 0) {
-        smn[threadIdx.x >> 6] = mn;
-        smx[threadIdx.x >> 6] = mx;
-    }
-    __syncthreads();
-    for (int w = 0; w < kRedBlock / 64; ++w) {
-        mn = jmin(mn, smn[w]);
-        mx = jmax(mx, smx[w]);
-    }
-}
-
-// FusionHelper.minMax (:105-138): a fixed tree (grid-stride partials, then one block),
-// so the result does not depend on scheduling -- min and max are order-independent.
-__global__ __launch_bounds__(kRedBlock) void k_minmax_partial(const float* __restrict__ c, int64_t n,
-                                                              float* __restrict__ part) {
-    float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
-    for (int64_t i = int64_t(blockIdx.x) * kRedBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kRedBlock) {
-        const float v = c[i];
-        mn = jmin(mn, v);
-        mx = jmax(mx, v);
-    }
-    block_minmax(mn, mx);
-    if (threadIdx.x == 0) {
-        part[2 * blockIdx.x] = mn;
-        part[2 * blockIdx.x + 1] = mx;
-    }
-}
-
-__global__ __launch_bounds__(kRedBlock) void k_minmax_final(const float* __restrict__ part, int nparts,
-                                                            float* __restrict__ mm) {
-    float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
-    for (int i = threadIdx.x; i < nparts; i += kRedBlock) {
-        mn = jmin(mn, part[2 * i]);
-        mx = jmax(mx, part[2 * i + 1]);
-    }
-    block_minmax(mn, mx);
-    if (threadIdx.x == 0) {
-        mm[0] = mn;
-        mm[1] = mx;
-    }
-}
+struct ContentMinMax {   // the rule of minmax.hpp's reduction
+    static __device__ __forceinline__ float mn(float a, float b) { return jmin(a, b); }
+    static __device__ __forceinline__ float mx(float a, float b) { return jmax(a, b); }
+};
 
 // FusionHelper.normalizeImage (:176-211): (c - min) / diff in float, skipped when the
 // range is NaN, infinite or 0
@@ -238,23 +193,12 @@ __global__ __launch_bounds__(kRedBlock) void k_normalise(float* __restrict__ c, 
     if (i < n) c[i] = (c[i] - mn) / diff;
 }
 
-// Util.createGaussianKernel1DDouble(sigma, true) (imglib1; restated after
-// oracle/dog_ref.gaussian_kernel_1d), cast to float and zero-padded for the kernel
+// gaussian_kernel(sigma), cast to float and zero-padded for the kernel
 std::vector<float> gaussian_taps(double sigma, int* K) {
-    const int size = std::max(3, 2 * int(3 * sigma + 0.5) + 1);
-    std::vector<double> g(size_t(size), 0.0);
-    const int c = size / 2;
-    const double two_sq = 2 * sigma * sigma;
-    for (int x = c; x >= 0; --x) {
-        const double v = std::exp(-double(x * x) / two_sq);
-        g[size_t(c - x)] = v;
-        g[size_t(c + x)] = v;
-    }
-    double s = 0.0;
-    for (double v : g) s += v;
-    std::vector<float> t(size_t(padded_taps(size)), 0.0f);
-    for (int i = 0; i < size; ++i) t[size_t(i)] = float(g[size_t(i)] / s);
-    *K = size;
+    const std::vector<double> g = gaussian_kernel(sigma);
+    *K = int(g.size());
+    std::vector<float> t(size_t(padded_taps(*K)), 0.0f);
+    for (size_t i = 0; i < g.size(); ++i) t[i] = float(g[i]);
     return t;
 }
 
@@ -289,15 +233,6 @@ void launch_pass(int axis, const float* in, const float* sub, float* out, const 
     SD_HIP(hipGetLastError());
 }
 
-bool on_device(const void* p, int dev) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();   // pageable host memory: not registered with HIP
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice && at.device == dev;
-}
-
 }  // namespace
 
 void check_content_sigmas(const double* sigma1, const double* sigma2) {
@@ -313,9 +248,8 @@ void check_content_sigmas(const double* sigma1, const double* sigma2) {
     }
 }
 
-// ContentBased.approximateEntropy on device buffers: img, out and tmp hold dims voxels
-// each (img is only read; out receives the weights).  Enqueued on s; the taps and the
-// reduction scratch are released after a synchronise.
+// (fusion.hpp)  Enqueued on s; the taps and the reduction scratch are released after a
+// synchronise.
 void content_weights_device(const float* img, const int64_t dims[3], const double* sigma1, const double* sigma2,
                             float* out, float* tmp, hipStream_t s) {
     check_content_sigmas(sigma1, sigma2);
@@ -338,12 +272,11 @@ void content_weights_device(const float* img, const int64_t dims[3], const doubl
     launch_pass(0, tmp, img, out, taps.p + off[3], K[3], dims, s);
     launch_pass(1, out, nullptr, tmp, taps.p + off[4], K[4], dims, s);
     launch_pass(2, tmp, nullptr, out, taps.p + off[5], K[5], dims, s);
-    const int parts = int(std::max<int64_t>(1, std::min<int64_t>(kRedGrid, ceil_div(n, kRedBlock))));
+    const int parts = minmax_parts(n);
     DBuf<float> red(size_t(2 * parts + 2));
     float* mm = red.p + 2 * parts;
     SD_CHECK(ceil_div(n, kRedBlock) < (int64_t(1) << 31), SPIMDECON_ERR_ARG, "view too large");
-    hipLaunchKernelGGL(k_minmax_partial, dim3(unsigned(parts)), dim3(kRedBlock), 0, s, out, n, red.p);
-    hipLaunchKernelGGL(k_minmax_final, dim3(1), dim3(kRedBlock), 0, s, red.p, parts, mm);
+    minmax_launch<ContentMinMax>(out, n, parts, red.p, mm, s);
     hipLaunchKernelGGL(k_normalise, dim3(unsigned(ceil_div(n, kRedBlock))), dim3(kRedBlock), 0, s, out, n, mm);
     SD_HIP(hipGetLastError());
     SD_HIP(hipStreamSynchronize(s));
@@ -353,36 +286,16 @@ void content_based_weights(const float* img, const int64_t* dims, const double* 
                            float* out, int device) {
     SD_CHECK(img && dims && out, SPIMDECON_ERR_ARG, "content-based weights: null argument");
     check_content_sigmas(sigma1, sigma2);
-    SD_CHECK(dims[0] >= 1 && dims[1] >= 1 && dims[2] >= 1 && dims[0] < (1 << 30) && dims[1] < (1 << 30) &&
-                 dims[2] < (1 << 30),
-             SPIMDECON_ERR_ARG, "content-based weights: bad dims");
+    const int64_t n = check_volume(dims, "content-based weights: bad dims", "content-based weights: bad dims");
     check_device(device);
     DeviceGuard guard(device);
-    hipStream_t s;
-    SD_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct SG {
-        hipStream_t s;
-        ~SG() { (void)hipStreamDestroy(s); }
-    } sg{s};
-    const int64_t n = dims[0] * dims[1] * dims[2];
+    ScopedStream st;
     DBuf<float> dimg, dout, tmp{size_t(n)};
-    const float* in = img;
-    if (!on_device(img, device)) {
-        dimg.alloc(size_t(n));
-        SD_HIP(hipMemcpyAsync(dimg.p, img, n * 4, hipMemcpyDefault, s));   // host or another device
-        in = dimg.p;
-    }
-    const bool out_dev = on_device(out, device);
-    float* o = out;
-    if (!out_dev) {
-        dout.alloc(size_t(n));
-        o = dout.p;
-    }
-    content_weights_device(in, dims, sigma1, sigma2, o, tmp.p, s);
-    if (!out_dev) {
-        SD_HIP(hipMemcpyAsync(out, o, n * 4, hipMemcpyDefault, s));
-        SD_HIP(hipStreamSynchronize(s));
-    }
+    const float* in = stage_in(img, n, device, dimg, st.s);
+    ImageDest dst(out, n, device);
+    content_weights_device(in, dims, sigma1, sigma2, dst.store(dout), tmp.p, st.s);
+    dst.copy_out(st.s);
+    if (!dst.out_dev) SD_HIP(hipStreamSynchronize(st.s));
 }
 
 }  // namespace spimdecon

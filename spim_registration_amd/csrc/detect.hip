@@ -12,15 +12,6 @@
 #include "detect_dev.hpp"
 
 namespace spimdecon {
-
-// dog_sort.hip
-size_t peak_sort_temp_bytes(int64_t n, int end_bit);
-void peak_sort(void* tmp, size_t tmp_bytes, const uint64_t* kin, uint64_t* kout, const uint32_t* vin,
-               uint32_t* vout, int64_t n, int end_bit, hipStream_t s);
-size_t point_select_temp_bytes(int64_t n);
-void point_select(void* tmp, size_t tmp_bytes, const spim_interest_point* in, const unsigned char* flags,
-                  spim_interest_point* out, int* nsel, int64_t n, hipStream_t s);
-
 namespace {
 
 // one wave-wide append; every lane of the wave must call it
@@ -347,15 +338,6 @@ __global__ void k_localize(const float* __restrict__ dog, Dims3 d, const PeakOut
     out[i] = o;
 }
 
-DogWork& dog_work(int dev) { return per_device<DogWork>(dev); }
-
-const float* stage_view(DogWork& w, const float* img, int64_t n, int device, hipStream_t s) {
-    if (is_device_ptr(img, device)) return img;
-    grow(w.in, size_t(n));
-    SD_HIP(hipMemcpyAsync(w.in.p, img, n * 4, hipMemcpyDefault, s));   // host or another device
-    return w.in.p;
-}
-
 // ---------------------------------------------------------------- the shared detection stage
 void stored_candidates(DogWork& w, const Dims3& d, const float* dogp, bool peaks_kernel, const PeakSink& pk,
                        hipStream_t s) {
@@ -490,7 +472,7 @@ struct DetectArgs {   // (what check_detector_args reads of a detector's paramet
 void detect_run(const float* img, const int64_t* dims, float min_peak, int find_min, int find_max, int T, int route,
                 int device, hipStream_t s, DogWork& w, DogRun& r) {
     const Dims3 d{dims[0], dims[1], dims[2]};
-    const float* in = stage_view(w, img, d.nx * d.ny * d.nz, device, s);
+    const float* in = stage_in(img, d.nx * d.ny * d.nz, device, w.in, s);
     detect_stored(w, d, in, min_peak, find_min ? 1 : 0, find_max ? 1 : 0, T, s, r, route);
 }
 
@@ -512,7 +494,7 @@ void detect_peaks(const float* img, const int64_t* dims, float min_peak, int fin
                   int device, spim_peak* peaks, int64_t max_peaks, int64_t* npeaks) {
     SD_CHECK(npeaks, SPIMDECON_ERR_ARG, "null argument");
     detect_check(img, dims, DetectArgs{0, T}, route);
-    with_detector(device, [&](DogWork& w, hipStream_t s) {
+    with_work<DogWork>(device, [&](DogWork& w, hipStream_t s) {
         DogRun r;
         detect_run(img, dims, min_peak, find_min, find_max, T, route, device, s, w, r);
         peaks_to_host(r, peaks, max_peaks, npeaks, s);
@@ -524,7 +506,7 @@ void detect_interest_points(const float* img, const int64_t* dims, float min_pea
                             int64_t max_out, int64_t* nout) {
     SD_CHECK(nout, SPIMDECON_ERR_ARG, "null argument");
     detect_check(img, dims, DetectArgs{localization, T}, route);
-    with_detector(device, [&](DogWork& w, hipStream_t s) {
+    with_work<DogWork>(device, [&](DogWork& w, hipStream_t s) {
         DogRun r;
         detect_run(img, dims, min_peak, find_min, find_max, T, route, device, s, w, r);
         points_from_peaks(w, r, localization, keep_thr, out, max_out, nout, s);
@@ -532,7 +514,7 @@ void detect_interest_points(const float* img, const int64_t* dims, float min_pea
 }
 
 void dog_release_workspace(int dev) {
-    with_workspace(dev, [](DogWork& w) {
+    with_work<DogWork>(dev, [](DogWork& w) {
         SD_HIP(hipDeviceSynchronize());
         w.release();
     });

@@ -6,7 +6,7 @@
 
 #include <algorithm>
 
-#include "common.hpp"
+#include "hostcall.hpp"
 
 namespace spimdecon {
 
@@ -47,8 +47,7 @@ struct LocOut {
 // more than the DoG itself).  One call at a time per device holds its mutex;
 // spim_dog_release_workspace frees it.  (The DOM detector and the downsampler stage their
 // input in `in` and write their image to `dog`: they add no buffer of their own.)
-struct DogWork {
-    std::mutex mu;
+struct DogWork : WorkBase {
     DBuf<float> in, dog, taps, mm, tmp_a, tmp_b, tmp_c, tmp_d;
     DBuf<float2> g12;
     DBuf<uint64_t> keys, keys_sorted;
@@ -61,42 +60,12 @@ struct DogWork {
     DBuf<unsigned char> flags, sel_tmp;
     DBuf<int> nsel;
     DBuf<PeakSink> sink;                   // the candidate kernels' sink, read at their flushes
-    // the calls' stream, created once (a stream per call cost ~1 ms of host time per
-    // 768^3 call: r3l trace, 1.17 ms before the first copy)
-    hipStream_t stream = nullptr;
-    hipStream_t get_stream() {
-        if (!stream) SD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        return stream;
-    }
     void release() {
-        if (stream) {
-            (void)hipStreamDestroy(stream);
-            stream = nullptr;
-        }
-        auto all = [](auto&... b) { (b.release(), ...); };
-        all(in, dog, taps, mm, tmp_a, tmp_b, tmp_c, tmp_d, g12, keys, keys_sorted, vals, vals_sorted, recs, peaks, count,
-            sort_tmp, loc, ips, ips_sel, flags, sel_tmp, nsel, sink);
+        release_stream();
+        release_all(in, dog, taps, mm, tmp_a, tmp_b, tmp_c, tmp_d, g12, keys, keys_sorted, vals, vals_sorted, recs,
+                    peaks, count, sort_tmp, loc, ips, ips_sel, flags, sel_tmp, nsel, sink);
     }
 };
-
-DogWork& dog_work(int dev);
-
-// ---------------------------------------------------------------- the call scaffold
-// body(w) on `device`, holding its workspace's mutex
-template <typename Body>
-void with_workspace(int device, Body&& body) {
-    check_device(device);
-    DeviceGuard guard(device);
-    DogWork& w = dog_work(device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    body(w);
-}
-
-// One detector call: body(w, s) with the workspace's stream (held under its mutex)
-template <typename Body>
-void with_detector(int device, Body&& body) {
-    with_workspace(device, [&](DogWork& w) { body(w, w.get_stream()); });
-}
 
 // The argument rules DoG and DoM share; `own()` runs the detector's own between the view's
 // and the localisation's.
@@ -110,28 +79,6 @@ void check_detector_args(const float* img, const int64_t* dims, const Params* p,
              "the reference either (Localization.java:90-96)");
     SD_CHECK(p->ij_threads >= 1 && p->ij_threads < (1 << 20), SPIMDECON_ERR_ARG, "ij_threads must be >= 1");
 }
-
-// the view of n voxels: read in place when it already lives in the device's HBM, else one
-// upload into w.in (from the host or another device)
-const float* stage_view(DogWork& w, const float* img, int64_t n, int device, hipStream_t s);
-
-// Where a call's image of n voxels goes: the caller's buffer when that is memory of the
-// device, else the workspace's w.dog, copied out to the caller's (if any) at the end.
-struct ImageDest {
-    float* out;            // the caller's buffer, or nullptr
-    bool out_dev;          // ... is device memory
-    int64_t n;
-    float* p = nullptr;    // where the kernels write; nullptr: the image is not stored
-    ImageDest(float* out, int64_t n, int device) : out(out), out_dev(out && is_device_ptr(out, device)), n(n) {}
-    float* store(DogWork& w) {
-        if (!p && !out_dev) grow(w.dog, size_t(n));
-        if (!p) p = out_dev ? out : w.dog.p;
-        return p;
-    }
-    void copy_out(hipStream_t s) const {
-        if (out && !out_dev) SD_HIP(hipMemcpyAsync(out, p, n * 4, hipMemcpyDefault, s));
-    }
-};
 
 // ---------------------------------------------------------------- the detection stage
 // the detector's image (on the device) and the reference-ordered candidate list (on the device)
@@ -191,5 +138,13 @@ void peaks_to_host(const DogRun& r, spim_peak* peaks, int64_t max_peaks, int64_t
 // kept when |fitted value| > keep_thr) of the candidates; out may be host or device memory
 void points_from_peaks(DogWork& w, const DogRun& r, int localization, float keep_thr, spim_interest_point* out,
                        int64_t max_out, int64_t* nout, hipStream_t s);
+
+// ---------------------------------------------------------------- dog_sort.hip
+size_t peak_sort_temp_bytes(int64_t n, int end_bit);
+void peak_sort(void* tmp, size_t tmp_bytes, const uint64_t* kin, uint64_t* kout, const uint32_t* vin,
+               uint32_t* vout, int64_t n, int end_bit, hipStream_t s);
+size_t point_select_temp_bytes(int64_t n);
+void point_select(void* tmp, size_t tmp_bytes, const spim_interest_point* in, const unsigned char* flags,
+                  spim_interest_point* out, int* nsel, int64_t n, hipStream_t s);
 
 }  // namespace spimdecon

@@ -760,29 +760,6 @@ void dog_sigmas(float sigma, const double image_sigma[3], double s1[3], double s
     }
 }
 
-// imglib1 Util.createGaussianKernel1DDouble(sigma, true)
-std::vector<double> gaussian_kernel(double sigma) {
-    std::vector<double> g;
-    if (sigma <= 0) {
-        g.assign(3, 0.0);
-        g[1] = 1.0;
-    } else {
-        const int size = std::max(3, 2 * int(3 * sigma + 0.5) + 1);
-        const double two_sq = 2 * sigma * sigma;
-        g.assign(size, 0.0);
-        const int c = size / 2;
-        for (int x = c; x >= 0; --x) {
-            const double val = std::exp(-(double(x) * x) / two_sq);
-            g[c - x] = val;
-            g[c + x] = val;
-        }
-    }
-    double sum = 0;
-    for (double v : g) sum += v;
-    for (double& v : g) v /= sum;
-    return g;
-}
-
 // CUDASeparableConvolutionFunctions.getCUDAKernels: pad to the smallest supported size
 int cuda_kernels(const double sig[3], std::vector<float> out[3]) {
     static const int sizes[5] = {7, 15, 31, 63, 127};
@@ -891,7 +868,7 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, in
     // (SPIMDECON_DOG_TRIM=0: every padded tap always)
     const int jt = dog_env("SPIMDECON_DOG_TRIM", 1) ? std::min(1, std::min(zero_lead(0), zero_lead(1))) : 0;
 
-    const float* in = stage_view(w, img, n, p->device, s);
+    const float* in = stage_in(img, n, p->device, w.in, s);
     grow(w.mm, 3 * 4096);
     const bool use_given = !(std::isnan(p->min_intensity) || std::isnan(p->max_intensity) ||
                              std::isinf(p->min_intensity) || std::isinf(p->max_intensity) ||
@@ -909,7 +886,7 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, in
     // the DoG image is stored when the caller or the localisation needs it -- and below, when
     // the split z stage or the separate passes do
     ImageDest dst(dog_out, n, p->device);
-    if (need_dog) dst.store(w);
+    if (need_dog) dst.store(w.dog);
     const int T = p->ij_threads;
     const int wmin = p->find_min ? 1 : 0, wmax = p->find_max ? 1 : 0;
     // what the kernels' addressing forms need, each named once
@@ -939,7 +916,7 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, in
     // (k_dog_zconv takes its plane indices the scalar way; k_dog_peaks needs the DoG below 4 GiB)
     const bool split = fused && dog_env("SPIMDECON_DOG_SPLIT", 1) != 0 && zscalar && img_4g;
     const int zc1 = std::max(1, dog_env("SPIMDECON_DOG_ZC_CHUNK", 256));
-    if (split) dst.store(w);
+    if (split) dst.store(w.dog);
     if (fused) {
         grow(w.g12, size_t(n));
         // (k_minmax's own range: the per-value range check is skipped; SPIMDECON_DOG_MM_EXACT=0
@@ -966,7 +943,7 @@ void dog_run(const float* img, const int64_t* dims, const spim_dog_params* p, in
         grow(w.tmp_b, size_t(n));
         grow(w.tmp_c, size_t(n));
         grow(w.tmp_d, size_t(n));
-        dst.store(w);
+        dst.store(w.dog);
         sep_pass(d, 0, in, in, kp(0, 0), kp(0, 1), K, oob, 0.f, w.tmp_a.p, w.tmp_b.p, false, 0.f, w.mm.p, s);
         sep_pass(d, 1, w.tmp_a.p, w.tmp_b.p, kp(1, 0), kp(1, 1), K, oob, 0.f, w.tmp_c.p, w.tmp_d.p, false,
                  0.f, nullptr, s);
@@ -1006,7 +983,7 @@ void dog_compute(const float* img, const int64_t* dims, const spim_dog_params* p
                  spim_peak* peaks, int64_t max_peaks, int64_t* npeaks) {
     SD_CHECK(npeaks && p, SPIMDECON_ERR_ARG, "null argument");
     const int oob = dog_oob(extension);
-    with_detector(p->device, [&](DogWork& w, hipStream_t s) {
+    with_work<DogWork>(p->device, [&](DogWork& w, hipStream_t s) {
         DogRun r;
         dog_run(img, dims, p, oob, dog_out, dog_out != nullptr, s, w, r);
         peaks_to_host(r, peaks, max_peaks, npeaks, s);
@@ -1018,7 +995,7 @@ void dog_interest_points(const float* img, const int64_t* dims, const spim_dog_p
                          float* dog_out, spim_interest_point* out, int64_t max_out, int64_t* nout) {
     SD_CHECK(nout && p, SPIMDECON_ERR_ARG, "null argument");
     const int oob = dog_oob(extension);
-    with_detector(p->device, [&](DogWork& w, hipStream_t s) {
+    with_work<DogWork>(p->device, [&](DogWork& w, hipStream_t s) {
         DogRun r;
         dog_run(img, dims, p, oob, dog_out, p->localization == 1 || dog_out != nullptr, s, w, r);
         points_from_peaks(w, r, p->localization, float(p->threshold), out, max_out, nout, s);

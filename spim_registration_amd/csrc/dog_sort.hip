@@ -7,7 +7,7 @@
 // compile and nothing else needs it.
 #include <hipcub/hipcub.hpp>
 
-#include "common.hpp"
+#include "detect.hpp"
 
 namespace spimdecon {
 

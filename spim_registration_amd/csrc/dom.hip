@@ -316,7 +316,7 @@ void dom_run(const float* img, const int64_t* dims, const spim_dom_params* p, fl
     b.vol1 = s1[0] * s1[1] * s1[2];
     b.vol2 = s2[0] * s2[1] * s2[2];
 
-    const float* in = stage_view(w, img, n, p->device, s);
+    const float* in = stage_in(img, n, p->device, w.in, s);
     // ProcessDOM.java:54-66 (the rule of ProcessDOG)
     grow(w.mm, 3 * 4096);   // {min, max, -, -, the per-block partials}
     static_assert(4 + 3 * kDomMmBlocks <= 3 * 4096, "partials beyond the min / max buffer");
@@ -333,7 +333,7 @@ void dom_run(const float* img, const int64_t* dims, const spim_dom_params* p, fl
         SD_HIP(hipGetLastError());
     }
     ImageDest dst(dom_out, n, p->device);
-    float* const domp = dst.store(w);
+    float* const domp = dst.store(w.dog);
     // DOM.java:47-53: where the boxes fit; elsewhere (everywhere, when they fit nowhere) zero
     const bool interior = d.nx > 2 * b.hm[0] && d.ny > 2 * b.hm[1] && d.nz > 2 * b.hm[2];
     const unsigned gf = unsigned(std::min<int64_t>(ceil_div(d.ny * d.nz, int64_t(kDomBlock / 64)), 8192));
@@ -367,7 +367,7 @@ void dom_compute(const float* img, const int64_t* dims, const spim_dom_params* p
                  int64_t max_peaks, int64_t* npeaks) {
     SD_CHECK(npeaks, SPIMDECON_ERR_ARG, "null argument");
     check_detector_args(img, dims, p, [&] { dom_check_params(p); });
-    with_detector(p->device, [&](DogWork& w, hipStream_t s) {
+    with_work<DogWork>(p->device, [&](DogWork& w, hipStream_t s) {
         DogRun r;
         dom_run(img, dims, p, dom_out, s, w, r);
         peaks_to_host(r, peaks, max_peaks, npeaks, s);
@@ -379,7 +379,7 @@ void dom_interest_points(const float* img, const int64_t* dims, const spim_dom_p
                          spim_interest_point* out, int64_t max_out, int64_t* nout) {
     SD_CHECK(nout, SPIMDECON_ERR_ARG, "null argument");
     check_detector_args(img, dims, p, [&] { dom_check_params(p); });
-    with_detector(p->device, [&](DogWork& w, hipStream_t s) {
+    with_work<DogWork>(p->device, [&](DogWork& w, hipStream_t s) {
         DogRun r;
         dom_run(img, dims, p, dom_out, s, w, r);
         points_from_peaks(w, r, p->localization, p->threshold, out, max_out, nout, s);

@@ -250,10 +250,10 @@ void downsample(const float* img, const int64_t* dims, const int32_t* factor, in
     SD_CHECK(dims[0] < (int64_t(1) << 30) && dims[1] < (int64_t(1) << 30) && dims[2] < (int64_t(1) << 30) &&
                  n < (int64_t(1) << 40) && dims[0] * dims[1] < (int64_t(1) << 31),
              SPIMDECON_ERR_ARG, "volume too large");
-    with_detector(device, [&](DogWork& w, hipStream_t s) {
-        const float* in = stage_view(w, img, n, device, s);
+    with_work<DogWork>(device, [&](DogWork& w, hipStream_t s) {
+        const float* in = stage_in(img, n, device, w.in, s);
         ImageDest dest(out, no, device);
-        float* const dst = dest.store(w);
+        float* const dst = dest.store(w.dog);
         const bool xy = lx || ly;
         if (!xy && !lz) {
             SD_HIP(hipMemcpyAsync(dst, in, n * 4, hipMemcpyDeviceToDevice, s));

@@ -336,17 +336,14 @@ void gh_descriptors(const double* pts, int64_t n, const spim_gh_params* p, int32
     pm_check_points(pts, n, "geometric hashing");
     SD_CHECK(neighbors && desc, SPIMDECON_ERR_ARG, "null argument");
     SD_CHECK(n >= kGhMinPoints, SPIMDECON_ERR_ARG, "geometric hashing: a descriptor needs 4 points");
-    check_device(p->device);
-    DeviceGuard guard(p->device);
-    GhWork& w = per_device<GhWork>(p->device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    hipStream_t s = w.get_stream();
-    const double* d = pm_stage_points(pts, n, p->device, w.pts_a, w.bad, s, "geometric hashing");
-    grow(w.desc_a, size_t(n) * 6);
-    gh_describe(d, int(n), w, w.desc_a.p, s);
-    SD_HIP(hipMemcpyAsync(neighbors, w.nbr.p, size_t(n) * 3 * sizeof(int), hipMemcpyDefault, s));
-    SD_HIP(hipMemcpyAsync(desc, w.desc_a.p, size_t(n) * 6 * sizeof(float), hipMemcpyDefault, s));
-    SD_HIP(hipStreamSynchronize(s));
+    with_work<GhWork>(p->device, [&](GhWork& w, hipStream_t s) {
+        const double* d = pm_stage_points(pts, n, p->device, w.pts_a, w.bad, s, "geometric hashing");
+        grow(w.desc_a, size_t(n) * 6);
+        gh_describe(d, int(n), w, w.desc_a.p, s);
+        SD_HIP(hipMemcpyAsync(neighbors, w.nbr.p, size_t(n) * 3 * sizeof(int), hipMemcpyDefault, s));
+        SD_HIP(hipMemcpyAsync(desc, w.desc_a.p, size_t(n) * 6 * sizeof(float), hipMemcpyDefault, s));
+        SD_HIP(hipStreamSynchronize(s));
+    });
 }
 
 void gh_match(const double* a, int64_t na, const double* b, int64_t nb, const spim_gh_params* p, int32_t* best_idx,

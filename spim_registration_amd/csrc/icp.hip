@@ -186,72 +186,69 @@ void icp_assign(const double* target, int64_t nt, const double* reference, int64
     SD_CHECK(nr == 0 || (nearest && dist), SPIMDECON_ERR_ARG, "null argument");
     *count = 0;
     *ambiguous = 0;
-    check_device(p->device);
-    DeviceGuard guard(p->device);
-    IcpWork& w = per_device<IcpWork>(p->device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    hipStream_t s = w.get_stream();
-    IcpModel mdl = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
-    if (model && is_device_ptr(model, p->device)) {
-        SD_HIP(hipMemcpyAsync(mdl.m, model, sizeof(mdl.m), hipMemcpyDeviceToHost, s));
+    with_work<IcpWork>(p->device, [&](IcpWork& w, hipStream_t s) {
+        IcpModel mdl = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0}};
+        if (model && is_device_ptr(model, p->device)) {
+            SD_HIP(hipMemcpyAsync(mdl.m, model, sizeof(mdl.m), hipMemcpyDeviceToHost, s));
+            SD_HIP(hipStreamSynchronize(s));
+        } else if (model) {
+            std::memcpy(mdl.m, model, sizeof(mdl.m));
+        }
+        const double* dt = nt ? pm_stage_points(target, nt, p->device, w.pts_t, w.bad, s, "icp") : nullptr;
+        const double* dr = nr ? pm_stage_points(reference, nr, p->device, w.pts_r, w.bad, s, "icp") : nullptr;
+        if (nr == 0) return;
+        grow(w.nearest, size_t(nr));
+        grow(w.dist, size_t(nr));
+        grow(w.stats, 3);
+        SD_HIP(hipMemsetAsync(w.stats.p, 0, 3 * sizeof(int64_t), s));
+        const unsigned gr = unsigned(ceil_div(nr, kIcpBlock));
+        if (nt == 0) {
+            hipLaunchKernelGGL(k_icp_fill, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), w.nearest.p, w.dist.p);
+            SD_HIP(hipGetLastError());
+        } else {
+            grow(w.tw, size_t(nt));
+            hipLaunchKernelGGL(k_icp_apply, dim3(unsigned(ceil_div(nt, kIcpBlock))), dim3(kIcpBlock), 0, s, dt, int(nt),
+                               mdl, w.tw.p, w.stats.p + 2);
+            SD_HIP(hipGetLastError());
+            // target split: 16,000 reference points are 63 blocks; aim at 2 blocks of 4 waves per CU
+            const int64_t rblocks = ceil_div(nr, kIcpRBlock);
+            const PmSplit sp = pm_split(p->t_split, rblocks, nt, kIcpTTile, 2, p->device, "icp");
+            grow(w.pd, size_t(nr) * sp.split);
+            grow(w.pi, size_t(nr) * sp.split);
+            hipLaunchKernelGGL(k_icp_assign, dim3(unsigned(rblocks), unsigned(sp.split)), dim3(kIcpRBlock), 0, s,
+                               w.tw.p, int(nt), dr, int(nr), sp.chunk, w.pd.p, w.pi.p);
+            SD_HIP(hipGetLastError());
+            grow(w.matched, size_t(nr));
+            grow(w.keep, size_t(nr));
+            grow(w.claims, size_t(nt));
+            SD_HIP(hipMemsetAsync(w.claims.p, 0, size_t(nt) * sizeof(int), s));
+            hipLaunchKernelGGL(k_icp_merge, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), int(sp.split), w.pd.p, w.pi.p,
+                               double(p->max_distance), w.nearest.p, w.dist.p, w.matched.p, w.claims.p);
+            SD_HIP(hipGetLastError());
+            hipLaunchKernelGGL(k_icp_resolve, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), w.nearest.p, w.matched.p,
+                               w.claims.p, w.keep.p, w.stats.p);
+            SD_HIP(hipGetLastError());
+            const int64_t dcap = std::min<int64_t>(cap, nr);
+            grow(w.match_t, size_t(std::max<int64_t>(dcap, 1)));
+            grow(w.match_r, size_t(std::max<int64_t>(dcap, 1)));
+            pm_compact(int(nr), w.keep.p, w.nearest.p, w.match_r.p, w.match_t.p, dcap, w.stats.p, s);
+        }
+        int64_t stats[3] = {0, 0, 0};
+        SD_HIP(hipMemcpyAsync(stats, w.stats.p, sizeof(stats), hipMemcpyDeviceToHost, s));
         SD_HIP(hipStreamSynchronize(s));
-    } else if (model) {
-        std::memcpy(mdl.m, model, sizeof(mdl.m));
-    }
-    const double* dt = nt ? pm_stage_points(target, nt, p->device, w.pts_t, w.bad, s, "icp") : nullptr;
-    const double* dr = nr ? pm_stage_points(reference, nr, p->device, w.pts_r, w.bad, s, "icp") : nullptr;
-    if (nr == 0) return;
-    grow(w.nearest, size_t(nr));
-    grow(w.dist, size_t(nr));
-    grow(w.stats, 3);
-    SD_HIP(hipMemsetAsync(w.stats.p, 0, 3 * sizeof(int64_t), s));
-    const unsigned gr = unsigned(ceil_div(nr, kIcpBlock));
-    if (nt == 0) {
-        hipLaunchKernelGGL(k_icp_fill, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), w.nearest.p, w.dist.p);
-        SD_HIP(hipGetLastError());
-    } else {
-        grow(w.tw, size_t(nt));
-        hipLaunchKernelGGL(k_icp_apply, dim3(unsigned(ceil_div(nt, kIcpBlock))), dim3(kIcpBlock), 0, s, dt, int(nt),
-                           mdl, w.tw.p, w.stats.p + 2);
-        SD_HIP(hipGetLastError());
-        // target split: 16,000 reference points are 63 blocks; aim at 2 blocks of 4 waves per CU
-        const int64_t rblocks = ceil_div(nr, kIcpRBlock);
-        const PmSplit sp = pm_split(p->t_split, rblocks, nt, kIcpTTile, 2, p->device, "icp");
-        grow(w.pd, size_t(nr) * sp.split);
-        grow(w.pi, size_t(nr) * sp.split);
-        hipLaunchKernelGGL(k_icp_assign, dim3(unsigned(rblocks), unsigned(sp.split)), dim3(kIcpRBlock), 0, s, w.tw.p,
-                           int(nt), dr, int(nr), sp.chunk, w.pd.p, w.pi.p);
-        SD_HIP(hipGetLastError());
-        grow(w.matched, size_t(nr));
-        grow(w.keep, size_t(nr));
-        grow(w.claims, size_t(nt));
-        SD_HIP(hipMemsetAsync(w.claims.p, 0, size_t(nt) * sizeof(int), s));
-        hipLaunchKernelGGL(k_icp_merge, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), int(sp.split), w.pd.p, w.pi.p,
-                           double(p->max_distance), w.nearest.p, w.dist.p, w.matched.p, w.claims.p);
-        SD_HIP(hipGetLastError());
-        hipLaunchKernelGGL(k_icp_resolve, dim3(gr), dim3(kIcpBlock), 0, s, int(nr), w.nearest.p, w.matched.p,
-                           w.claims.p, w.keep.p, w.stats.p);
-        SD_HIP(hipGetLastError());
-        const int64_t dcap = std::min<int64_t>(cap, nr);
-        grow(w.match_t, size_t(std::max<int64_t>(dcap, 1)));
-        grow(w.match_r, size_t(std::max<int64_t>(dcap, 1)));
-        pm_compact(int(nr), w.keep.p, w.nearest.p, w.match_r.p, w.match_t.p, dcap, w.stats.p, s);
-    }
-    int64_t stats[3] = {0, 0, 0};
-    SD_HIP(hipMemcpyAsync(stats, w.stats.p, sizeof(stats), hipMemcpyDeviceToHost, s));
-    SD_HIP(hipStreamSynchronize(s));
-    SD_CHECK(!stats[2], SPIMDECON_ERR_ARG, "icp: non-finite coordinates under the model");
-    SD_HIP(hipMemcpyAsync(nearest, w.nearest.p, size_t(nr) * sizeof(int), hipMemcpyDefault, s));
-    SD_HIP(hipMemcpyAsync(dist, w.dist.p, size_t(nr) * sizeof(float), hipMemcpyDefault, s));
-    *count = stats[0];
-    *ambiguous = stats[1];
-    if (*count <= cap && *count) {
-        SD_HIP(hipMemcpyAsync(match_t, w.match_t.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
-        SD_HIP(hipMemcpyAsync(match_r, w.match_r.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
-    }
-    SD_HIP(hipStreamSynchronize(s));
-    SD_CHECK(*count <= cap, SPIMDECON_ERR_ARG,
-             "icp: " + std::to_string(*count) + " matches beyond the capacity " + std::to_string(cap));
+        SD_CHECK(!stats[2], SPIMDECON_ERR_ARG, "icp: non-finite coordinates under the model");
+        SD_HIP(hipMemcpyAsync(nearest, w.nearest.p, size_t(nr) * sizeof(int), hipMemcpyDefault, s));
+        SD_HIP(hipMemcpyAsync(dist, w.dist.p, size_t(nr) * sizeof(float), hipMemcpyDefault, s));
+        *count = stats[0];
+        *ambiguous = stats[1];
+        if (*count <= cap && *count) {
+            SD_HIP(hipMemcpyAsync(match_t, w.match_t.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
+            SD_HIP(hipMemcpyAsync(match_r, w.match_r.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
+        }
+        SD_HIP(hipStreamSynchronize(s));
+        SD_CHECK(*count <= cap, SPIMDECON_ERR_ARG,
+                 "icp: " + std::to_string(*count) + " matches beyond the capacity " + std::to_string(cap));
+    });
 }
 
 }  // namespace

@@ -18,17 +18,11 @@
 #include <cstring>
 #include <vector>
 
-#include "common.hpp"
+#include "fusion.hpp"
+#include "hostcall.hpp"
 #include "resample.hpp"
-#include "spimdecon.h"
 
 namespace spimdecon {
-void check_device(int dev);
-// content_weights.hip
-void check_content_sigmas(const double* sigma1, const double* sigma2);
-void content_weights_device(const float* img, const int64_t dims[3], const double* sigma1, const double* sigma2,
-                            float* out, float* tmp, hipStream_t s);
-
 namespace {
 
 constexpr int kIpBlock = 256;
@@ -249,12 +243,8 @@ void prepare_inputs(int nviews, const spim_view_source* views, const spim_input_
     SD_CHECK(p->ij_threads >= 1, SPIMDECON_ERR_ARG, "ij_threads must be >= 1");
     check_device(p->device);
     DeviceGuard guard(p->device);
-    hipStream_t s;
-    SD_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct SG {
-        hipStream_t s;
-        ~SG() { (void)hipStreamDestroy(s); }
-    } sg{s};
+    ScopedStream st;
+    const hipStream_t s = st.s;
     const int64_t nx = p->bb_dims[0], ny = p->bb_dims[1], nz = p->bb_dims[2];
     const int64_t n = nx * ny * nz;
     const unsigned grid = unsigned(ceil_div(n, int64_t(kIpBlock)));
@@ -278,12 +268,9 @@ void prepare_inputs(int nviews, const spim_view_source* views, const spim_input_
     }
     for (int v = 0; v < nviews; ++v) {
         const spim_view_source& vs = views[v];
-        SD_CHECK(vs.img && vs.dims[0] >= 1 && vs.dims[1] >= 1 && vs.dims[2] >= 1, SPIMDECON_ERR_ARG,
-                 "bad view source");
-        SD_CHECK(vs.dims[0] < (1 << 30) && vs.dims[1] < (1 << 30) && vs.dims[2] < (1 << 30), SPIMDECON_ERR_ARG,
-                 "view too large");
+        SD_CHECK(vs.img, SPIMDECON_ERR_ARG, "bad view source");
+        const int64_t sn = check_volume(vs.dims, "bad view source", "view too large");
         ViewArgs a{};
-        const int64_t sn = vs.dims[0] * vs.dims[1] * vs.dims[2];
         DBuf<float> dsrc;
         if (p->src_on_device) {
             a.src = vs.img;
@@ -359,7 +346,6 @@ void prepare_inputs(int nviews, const spim_view_source* views, const spim_input_
     if (avg_overlap) *avg_overlap = av;
 }
 
-// sigma1 / sigma2 (nviews x 3, both or neither): content-based weights per view
 void fuse_weighted_average(int nviews, const spim_view_source* views, const spim_fusion_params* p,
                            const float* borders, const float* ranges, const double* sigma1, const double* sigma2,
                            float* out) {
@@ -372,12 +358,8 @@ void fuse_weighted_average(int nviews, const spim_view_source* views, const spim
     SD_CHECK(p->interpolation == 0 || p->interpolation == 1, SPIMDECON_ERR_ARG, "interpolation must be 0 or 1");
     check_device(p->device);
     DeviceGuard guard(p->device);
-    hipStream_t s;
-    SD_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct SG {
-        hipStream_t s;
-        ~SG() { (void)hipStreamDestroy(s); }
-    } sg{s};
+    ScopedStream st;
+    const hipStream_t s = st.s;
     const int64_t nx = p->bb_dims[0], ny = p->bb_dims[1], nz = p->bb_dims[2];
     const int64_t n = nx * ny * nz;
     const std::vector<double> lut = blending_lut();
@@ -387,10 +369,8 @@ void fuse_weighted_average(int nviews, const spim_view_source* views, const spim
     std::vector<FuseView> fv(nviews);
     for (int v = 0; v < nviews; ++v) {
         const spim_view_source& vs = views[v];
-        SD_CHECK(vs.img && vs.dims[0] >= 1 && vs.dims[1] >= 1 && vs.dims[2] >= 1 && vs.dims[0] < (1 << 30) &&
-                     vs.dims[1] < (1 << 30) && vs.dims[2] < (1 << 30),
-                 SPIMDECON_ERR_ARG, "bad view source");
-        const int64_t sn = vs.dims[0] * vs.dims[1] * vs.dims[2];
+        SD_CHECK(vs.img, SPIMDECON_ERR_ARG, "bad view source");
+        const int64_t sn = check_volume(vs.dims, "bad view source", "bad view source");
         if (p->src_on_device) {
             fv[v].src = vs.img;
         } else {

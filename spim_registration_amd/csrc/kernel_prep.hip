@@ -2,6 +2,7 @@
 // exponential / compound kernels (spim/process/fusion/deconvolution/MVDeconFFT.java:162-333,
 // AdjustInput.java:29-100, Mirror.java:31-108).  Kernels are tiny (<= ~51^3);
 // these are single-launch, latency-bound setup kernels.
+#include "hostcall.hpp"
 #include "kernel_prep.hpp"
 
 namespace spimdecon {
@@ -209,9 +210,8 @@ void prepare_kernels_gpu(std::vector<HostKernel>& k1, std::vector<HostKernel>& k
     SD_CHECK(psftype >= 0 && psftype <= 3, SPIMDECON_ERR_ARG, "unknown psftype");
     const int V = int(k1.size());
     SD_CHECK(V >= 1, SPIMDECON_ERR_ARG, "no views");
-    hipStream_t s;
-    SD_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } sg{s};
+    ScopedStream st;
+    const hipStream_t s = st.s;
 
     std::vector<DevKernel> K1(V);
     for (int v = 0; v < V; ++v) {

@@ -8,7 +8,7 @@
 #include <algorithm>
 #include <cfloat>
 
-#include "common.hpp"
+#include "hostcall.hpp"
 
 namespace spimdecon {
 
@@ -16,14 +16,8 @@ constexpr double kJavaDoubleMax = DBL_MAX;   // Double.MAX_VALUE
 
 // What every matcher's per-device workspace starts with.  Grown on demand and kept between
 // calls; one call at a time per matcher and device holds mu.
-struct PmWork {
-    std::mutex mu;
-    hipStream_t stream = nullptr;
+struct PmWork : WorkBase {
     DBuf<int> bad;   // pm_stage_points' flag
-    hipStream_t get_stream() {
-        if (!stream) SD_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-        return stream;
-    }
 };
 
 // the buffers of pm_match_candidates
@@ -82,41 +76,38 @@ void pm_match_candidates(const char* who, int min_points, int dev, const double*
     SD_CHECK(count && cap >= 0 && (cap == 0 || (cand_a && cand_b)), SPIMDECON_ERR_ARG, "null argument");
     SD_CHECK(na == 0 || (best_idx && best && second), SPIMDECON_ERR_ARG, "null argument");
     *count = 0;
-    check_device(dev);
-    DeviceGuard guard(dev);
-    W& w = per_device<W>(dev);
-    std::lock_guard<std::mutex> lk(w.mu);
-    hipStream_t s = w.get_stream();
-    const double* da = na ? pm_stage_points(a, na, dev, w.pts_a, w.bad, s, who) : nullptr;
-    const double* db = nb ? pm_stage_points(b, nb, dev, w.pts_b, w.bad, s, who) : nullptr;
-    if (na == 0) return;
-    grow(w.best, size_t(na));
-    grow(w.second, size_t(na));
-    grow(w.idx, size_t(na));
-    if (na < min_points || nb < min_points) {
-        pm_fill(int(na), w.best.p, w.second.p, w.idx.p, s);
-    } else {
-        grow(w.flag, size_t(na));
-        run(w, da, db, s);
-        grow(w.count, 1);
-        const int64_t dcap = std::min<int64_t>(cap, na);
-        grow(w.cand_a, size_t(std::max<int64_t>(dcap, 1)));
-        grow(w.cand_b, size_t(std::max<int64_t>(dcap, 1)));
-        pm_compact(int(na), w.flag.p, w.idx.p, w.cand_a.p, w.cand_b.p, dcap, w.count.p, s);
-        SD_HIP(hipMemcpyAsync(count, w.count.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    }
-    SD_HIP(hipMemcpyAsync(best_idx, w.idx.p, size_t(na) * sizeof(int), hipMemcpyDefault, s));
-    SD_HIP(hipMemcpyAsync(best, w.best.p, size_t(na) * sizeof(double), hipMemcpyDefault, s));
-    SD_HIP(hipMemcpyAsync(second, w.second.p, size_t(na) * sizeof(double), hipMemcpyDefault, s));
-    SD_HIP(hipStreamSynchronize(s));
-    SD_CHECK(*count <= cap, SPIMDECON_ERR_ARG,
-             std::string(who) + ": " + std::to_string(*count) + " candidates beyond the capacity " +
-                 std::to_string(cap));
-    if (*count) {
-        SD_HIP(hipMemcpyAsync(cand_a, w.cand_a.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
-        SD_HIP(hipMemcpyAsync(cand_b, w.cand_b.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
+    with_work<W>(dev, [&](W& w, hipStream_t s) {
+        const double* da = na ? pm_stage_points(a, na, dev, w.pts_a, w.bad, s, who) : nullptr;
+        const double* db = nb ? pm_stage_points(b, nb, dev, w.pts_b, w.bad, s, who) : nullptr;
+        if (na == 0) return;
+        grow(w.best, size_t(na));
+        grow(w.second, size_t(na));
+        grow(w.idx, size_t(na));
+        if (na < min_points || nb < min_points) {
+            pm_fill(int(na), w.best.p, w.second.p, w.idx.p, s);
+        } else {
+            grow(w.flag, size_t(na));
+            run(w, da, db, s);
+            grow(w.count, 1);
+            const int64_t dcap = std::min<int64_t>(cap, na);
+            grow(w.cand_a, size_t(std::max<int64_t>(dcap, 1)));
+            grow(w.cand_b, size_t(std::max<int64_t>(dcap, 1)));
+            pm_compact(int(na), w.flag.p, w.idx.p, w.cand_a.p, w.cand_b.p, dcap, w.count.p, s);
+            SD_HIP(hipMemcpyAsync(count, w.count.p, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+        }
+        SD_HIP(hipMemcpyAsync(best_idx, w.idx.p, size_t(na) * sizeof(int), hipMemcpyDefault, s));
+        SD_HIP(hipMemcpyAsync(best, w.best.p, size_t(na) * sizeof(double), hipMemcpyDefault, s));
+        SD_HIP(hipMemcpyAsync(second, w.second.p, size_t(na) * sizeof(double), hipMemcpyDefault, s));
         SD_HIP(hipStreamSynchronize(s));
-    }
+        SD_CHECK(*count <= cap, SPIMDECON_ERR_ARG,
+                 std::string(who) + ": " + std::to_string(*count) + " candidates beyond the capacity " +
+                     std::to_string(cap));
+        if (*count) {
+            SD_HIP(hipMemcpyAsync(cand_a, w.cand_a.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
+            SD_HIP(hipMemcpyAsync(cand_b, w.cand_b.p, size_t(*count) * sizeof(int), hipMemcpyDefault, s));
+            SD_HIP(hipStreamSynchronize(s));
+        }
+    });
 }
 
 }  // namespace spimdecon

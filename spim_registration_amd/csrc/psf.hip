@@ -20,7 +20,7 @@
 
 #include <memory>
 
-#include "common.hpp"
+#include "hostcall.hpp"
 #include "resample.hpp"
 #include "spimdecon.h"
 
@@ -226,12 +226,6 @@ Dim3 dim3_of(const int64_t* d, const char* what) {
 
 unsigned grid_for(int64_t n) { return unsigned(ceil_div(n, int64_t(kPsfBlock))); }
 
-struct Stream {
-    hipStream_t s{};
-    Stream() { SD_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
-    ~Stream() { (void)hipStreamDestroy(s); }
-};
-
 // transformPSF (:309-346): odd size that holds the transformed box, and the
 // offset keeping model(dim / 2) at the centre voxel
 void transformed_size(const int64_t size[3], const double* m, int64_t out[3], double off[3]) {
@@ -284,7 +278,7 @@ void transform_psf(const float* psf, const int64_t* psf_size, const double* mode
     const Dim3 s = dim3_of(psf_size, "psf");
     check_device(device);
     DeviceGuard guard(device);
-    Stream st;
+    ScopedStream st;
     DBuf<float> dp(s.n());
     SD_HIP(hipMemcpyAsync(dp.p, psf, s.n() * 4, hipMemcpyHostToDevice, st.s));
     int64_t ts[3];
@@ -303,7 +297,7 @@ namespace {
 // streams per call cost a hipMalloc / hipFree (which synchronises the device) per buffer
 // and view: the C4 pipeline's PSF stage spent most of its time there.
 struct PsfWork {
-    Stream st;
+    ScopedStream st;
     DBuf<float> dimg, dpsf, samp, dt;
     DBuf<double> dloc, mm;
 };
@@ -402,14 +396,13 @@ struct PsfJob {
 void extract_psf(const float* img, const int64_t* dims, int img_on_device, const double* locations, int64_t nloc,
                  const int64_t* psf_size, const double* model, float* psf_original, float* psf_transformed,
                  int device) {
-    check_device(device);
-    DeviceGuard guard(device);
-    PsfPool& pool = per_device<PsfPool>(device);
-    std::lock_guard<std::mutex> lk(pool.mu);
-    if (pool.w.empty()) pool.w.emplace_back(new PsfWork());
-    PsfJob job(*pool.w[0], img, dims, img_on_device, locations, nloc, psf_size, model, psf_original, psf_transformed);
-    job.launch();
-    job.finish();
+    with_work<PsfPool>(device, [&](PsfPool& pool) {
+        if (pool.w.empty()) pool.w.emplace_back(new PsfWork());
+        PsfJob job(*pool.w[0], img, dims, img_on_device, locations, nloc, psf_size, model, psf_original,
+                   psf_transformed);
+        job.launch();
+        job.finish();
+    });
 }
 
 void extract_psfs(int nviews, const float* const* imgs, const int64_t* dims, int img_on_device,
@@ -417,19 +410,17 @@ void extract_psfs(int nviews, const float* const* imgs, const int64_t* dims, int
                   const double* models, float* const* psf_original, float* const* psf_transformed, int device) {
     SD_CHECK(nviews >= 0 && (nviews == 0 || (imgs && dims && locations && nlocations && psf_original)),
              SPIMDECON_ERR_ARG, "null argument");
-    check_device(device);
-    DeviceGuard guard(device);
-    PsfPool& pool = per_device<PsfPool>(device);
-    std::lock_guard<std::mutex> lk(pool.mu);
-    while (int(pool.w.size()) < nviews) pool.w.emplace_back(new PsfWork());
-    std::vector<std::unique_ptr<PsfJob>> jobs;
-    jobs.reserve(size_t(nviews));
-    for (int v = 0; v < nviews; ++v)
-        jobs.emplace_back(new PsfJob(*pool.w[size_t(v)], imgs[v], dims + 3 * v, img_on_device, locations[v],
-                                     nlocations[v], psf_size, models ? models + 12 * v : nullptr, psf_original[v],
-                                     psf_transformed ? psf_transformed[v] : nullptr));
-    for (auto& j : jobs) j->launch();
-    for (auto& j : jobs) j->finish();
+    with_work<PsfPool>(device, [&](PsfPool& pool) {
+        while (int(pool.w.size()) < nviews) pool.w.emplace_back(new PsfWork());
+        std::vector<std::unique_ptr<PsfJob>> jobs;
+        jobs.reserve(size_t(nviews));
+        for (int v = 0; v < nviews; ++v)
+            jobs.emplace_back(new PsfJob(*pool.w[size_t(v)], imgs[v], dims + 3 * v, img_on_device, locations[v],
+                                         nlocations[v], psf_size, models ? models + 12 * v : nullptr,
+                                         psf_original[v], psf_transformed ? psf_transformed[v] : nullptr));
+        for (auto& j : jobs) j->launch();
+        for (auto& j : jobs) j->finish();
+    });
 }
 
 void average_transformed_psf(int npsf, const float* const* psfs, const int64_t* psf_dims, float* avg,
@@ -448,7 +439,7 @@ void average_transformed_psf(int npsf, const float* const* psfs, const int64_t* 
     const Dim3 md = dim3_of(m, "average psf");
     check_device(device);
     DeviceGuard guard(device);
-    Stream st;
+    ScopedStream st;
     std::vector<DBuf<float>> dp(npsf);
     std::vector<PsfRef> refs(npsf);
     for (int k = 0; k < npsf; ++k) {
@@ -484,7 +475,7 @@ void max_projection(const float* img, const int64_t* dims, int min_dim, float* o
     SD_CHECK(img, SPIMDECON_ERR_ARG, "null image");
     check_device(device);
     DeviceGuard guard(device);
-    Stream st;
+    ScopedStream st;
     DBuf<float> di(s.n());
     SD_HIP(hipMemcpyAsync(di.p, img, s.n() * 4, hipMemcpyHostToDevice, st.s));
     const int64_t no = out_dims[0] * out_dims[1];

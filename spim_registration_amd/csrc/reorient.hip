@@ -281,32 +281,10 @@ struct RoWork : PmWork {
     DBuf<int> pij, far_ij, flags;
     DBuf<int64_t> idx;
     void release() {
-        if (stream) {
-            (void)hipStreamDestroy(stream);
-            stream = nullptr;
-        }
-        bad.release();
-        stage.release();
-        world.release();
-        pd.release();
-        part.release();
-        boxes.release();
-        far_d.release();
-        pij.release();
-        far_ij.release();
-        flags.release();
-        idx.release();
+        release_stream();
+        release_all(bad, stage, world, pd, part, boxes, far_d, pij, far_ij, flags, idx);
     }
 };
-
-template <typename Body>
-void with_ro_work(int device, Body&& body) {
-    check_device(device);
-    DeviceGuard guard(device);
-    RoWork& w = per_device<RoWork>(device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    body(w, w.get_stream());
-}
 
 // the matchers' rules for a point list, every message led by the caller's name
 void ro_check_points(const double* pts, int64_t n, const char* who) {
@@ -440,7 +418,7 @@ void far_pair_call(const double* pts, int64_t n, int device, int32_t* i, int32_t
     SD_CHECK(i && j && d2, SPIMDECON_ERR_ARG, "farthest_pair: null argument");
     ro_check_points(pts, n, who);
     SD_CHECK(n >= 2, SPIMDECON_ERR_ARG, "farthest_pair: at least two points are required");
-    with_ro_work(device, [&](RoWork& w, hipStream_t s) {
+    with_work<RoWork>(device, [&](RoWork& w, hipStream_t s) {
         const double* d = pm_stage_points(pts, n, device, w.world, w.bad, s, who);
         const FarPair f = far_pair_device(w, d, n, 0, device, s, who);
         *i = f.p1;
@@ -456,7 +434,7 @@ void axis_boxes_call(const double* pts, int64_t n, const double* mats, int m, bo
              std::string(who) + ": 1 .. " + std::to_string(kRoMaxMats) + " matrices");
     ro_check_points(pts, n, who);
     SD_CHECK(n >= 1, SPIMDECON_ERR_ARG, std::string(who) + ": at least one point is required");
-    with_ro_work(device, [&](RoWork& w, hipStream_t s) {
+    with_work<RoWork>(device, [&](RoWork& w, hipStream_t s) {
         const double* d = pm_stage_points(pts, n, device, w.world, w.bad, s, who);
         axis_boxes_device(w, d, n, mats, m, raw, out, s);
     });
@@ -497,7 +475,7 @@ void reorient_bounding_box(int n_views, const double* const* lists, const int64_
                             : "reorient: at least one point is required");
     res->n_points = n;
     const int dev = p->device;
-    with_ro_work(dev, [&](RoWork& w, hipStream_t s) {
+    with_work<RoWork>(dev, [&](RoWork& w, hipStream_t s) {
         grow(w.world, size_t(3 * n));
         grow(w.stage, size_t(3 * std::max<int64_t>(max_list, 1)));
         grow(w.flags, 2);
@@ -600,16 +578,6 @@ void reorient_bounding_box(int n_views, const double* const* lists, const int64_
     }
 }
 
-void release_ro_work(int device) {
-    SD_CHECK(device >= 0, SPIMDECON_ERR_ARG, "bad device");
-    PerDevice<RoWork> all = per_device_all<RoWork>();
-    auto it = all.by_dev.find(device);
-    if (it == all.by_dev.end() || !it->second) return;
-    DeviceGuard guard(device);
-    std::lock_guard<std::mutex> lk(it->second->mu);
-    it->second->release();
-}
-
 }  // namespace
 }  // namespace spimdecon
 
@@ -648,5 +616,5 @@ extern "C" int spim_reorient_bounding_box(int n_views, const double* const* list
 }
 
 extern "C" int spim_reorient_release_workspace(int device) {
-    return guarded([&] { release_ro_work(device); });
+    return guarded([&] { release_work<RoWork>(device); });
 }

@@ -205,18 +205,15 @@ void rgldm_descriptors(const double* pts, int64_t n, const spim_rgldm_params* p,
     pm_check_points(pts, n, "rgldm");
     SD_CHECK(neighbors && rel, SPIMDECON_ERR_ARG, "null argument");
     SD_CHECK(n >= m + 1, SPIMDECON_ERR_ARG, "rgldm: a descriptor needs num_neighbors + redundancy + 1 points");
-    check_device(p->device);
-    DeviceGuard guard(p->device);
-    RgWork& w = per_device<RgWork>(p->device);
-    std::lock_guard<std::mutex> lk(w.mu);
-    hipStream_t s = w.get_stream();
-    const double* d = pm_stage_points(pts, n, p->device, w.pts_a, w.bad, s, "rgldm");
-    grow(w.nbr_a, size_t(n) * m);
-    grow(w.rel_a, size_t(n) * m * 3);
-    pm_knn(d, int(n), m, w.nbr_a.p, w.rel_a.p, s);
-    SD_HIP(hipMemcpyAsync(neighbors, w.nbr_a.p, size_t(n) * m * sizeof(int), hipMemcpyDefault, s));
-    SD_HIP(hipMemcpyAsync(rel, w.rel_a.p, size_t(n) * m * 3 * sizeof(double), hipMemcpyDefault, s));
-    SD_HIP(hipStreamSynchronize(s));
+    with_work<RgWork>(p->device, [&](RgWork& w, hipStream_t s) {
+        const double* d = pm_stage_points(pts, n, p->device, w.pts_a, w.bad, s, "rgldm");
+        grow(w.nbr_a, size_t(n) * m);
+        grow(w.rel_a, size_t(n) * m * 3);
+        pm_knn(d, int(n), m, w.nbr_a.p, w.rel_a.p, s);
+        SD_HIP(hipMemcpyAsync(neighbors, w.nbr_a.p, size_t(n) * m * sizeof(int), hipMemcpyDefault, s));
+        SD_HIP(hipMemcpyAsync(rel, w.rel_a.p, size_t(n) * m * 3 * sizeof(double), hipMemcpyDefault, s));
+        SD_HIP(hipStreamSynchronize(s));
+    });
 }
 
 void rgldm_match(const double* a, int64_t na, const double* b, int64_t nb, const spim_rgldm_params* p,

@@ -4,6 +4,7 @@
 // Gaussians of 63 / 127 taps.  Accumulation order = tap order in float32 (the oracle's bits).
 #include <algorithm>
 
+#include "hostcall.hpp"
 #include "sepconv.hpp"
 
 namespace spimdecon {
@@ -335,9 +336,8 @@ void separable_convolve(float* image, const float* kx, const float* ky, const fl
     SD_CHECK((!cx || kx) && (!cy || ky) && (!cz || kz), SPIMDECON_ERR_ARG, "null kernel");
     check_device(dev);
     DeviceGuard guard(dev);
-    hipStream_t s;
-    SD_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct SG { hipStream_t s; ~SG() { (void)hipStreamDestroy(s); } } sg{s};
+    ScopedStream st;
+    const hipStream_t s = st.s;
     const Dims3 d{w, h, dd};
     const int64_t n = int64_t(w) * h * dd;
     DBuf<float> a(n), b(n), dk(3 * size_t(K));

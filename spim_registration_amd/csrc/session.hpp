@@ -37,6 +37,9 @@
 
 namespace spimdecon {
 
+// part idx of nparts of [0, nz): the first nz % nparts parts hold one plane more
+void slab_range(int64_t nz, int nparts, int idx, int64_t* z0, int64_t* z1);
+
 struct SlabState {
     int grp = 0;           // device group (index into Session::groups_)
     SlabGeom g{};

@@ -41,6 +41,7 @@ FILTER_CASES = [
     ((9, 31, 257), 3),
     ((70, 45, 130), 12),       # windows crossing tile seams on all three axes
     ((5, 200, 66), 64),        # the largest supported radius
+    ((3, 5, 67), 2),           # no extent a multiple of any tile, narrower than the halo along z
 ]
 
 
@@ -59,10 +60,30 @@ def filter_refs():
     return refs
 
 
+def staged(img, on_device):
+    """a private copy of img where the call shall find it, and its address"""
+    import torch
+    a = torch.from_numpy(img.copy()).cuda() if on_device else img.copy()
+    torch.cuda.synchronize()   # the library runs on its own stream
+    return a, C.c_void_p(a.data_ptr() if on_device else a.ctypes.data)
+
+
+def dims_of(img):
+    return (C.c_int64 * 3)(*img.shape[::-1])
+
+
 @pytest.mark.parametrize("shape,r", FILTER_CASES)
-def test_min_filter_host_and_device(gpu, filter_refs, shape, r):
+def test_min_filter_host_and_device(gpu, lib, filter_refs, shape, r):
     import torch
     img, want = filter_refs[(shape, r)]
+    # the C entry with every pairing of a host / device-resident image and result
+    for src_dev in (False, True):
+        for out_dev in (False, True):
+            src, sp = staged(img, src_dev)
+            out, op = staged(np.zeros_like(img), out_dev)
+            assert lib.spim_min_filter(sp, dims_of(img), r, 0, op) == 0
+            np.testing.assert_array_equal(u32(out), u32(want), err_msg=f"{src_dev} {out_dev}")
+            np.testing.assert_array_equal(u32(src), u32(img))       # the input is only read
     got = bb.min_filter(img, r)
     assert isinstance(got, np.ndarray) and got.shape == img.shape
     np.testing.assert_array_equal(u32(got), u32(want))
@@ -150,8 +171,8 @@ def test_threshold_bounds(gpu):
 
 
 @pytest.mark.parametrize("shape,r,background", [((9, 31, 257), 3, 5.0), ((70, 45, 130), 12, 40.0),
-                                                ((3, 5, 7), 50, 5.0)])
-def test_segment_bounds_is_the_composition(gpu, shape, r, background):
+                                                ((3, 5, 7), 50, 5.0), ((3, 5, 67), 1, 5.0)])
+def test_segment_bounds_is_the_composition(gpu, lib, shape, r, background):
     import torch
     img = np.abs(random_image(shape, 11)) * 0.02
     nz, ny, nx = shape
@@ -177,6 +198,19 @@ def test_segment_bounds_is_the_composition(gpu, shape, r, background):
         want["bounds_min"], want["bounds_max"], want["found"])
     assert host["threshold"] == want["threshold"]
     np.testing.assert_array_equal(u32(host["filtered"]), u32(want["filtered"]))
+    np.testing.assert_array_equal(u32(filt), u32(want["filtered"]))
+    # the C entry with every pairing of a host / device-resident image and `filtered`, and without it
+    for src_dev in (False, True):
+        for out_dev in (False, True, None):
+            src, sp = staged(img, src_dev)
+            out, op = staged(np.zeros_like(img), out_dev) if out_dev is not None else (None, None)
+            res = _lib.SegmentResult()
+            assert lib.spim_segment_bounds(sp, dims_of(img), background, r, 0, op, C.byref(res)) == 0
+            np.testing.assert_array_equal(u32((res.min, res.max)), u32((mn, mx)))
+            assert res.threshold == thr
+            assert (tuple(res.bounds_min), tuple(res.bounds_max), bool(res.found)) == (lo, hi, found)
+            if out is not None:
+                np.testing.assert_array_equal(u32(out), u32(filt), err_msg=f"{src_dev} {out_dev}")
 
 
 @pytest.fixture(scope="module")

@@ -24,6 +24,7 @@ CASES = {
     "b_long_kernels": ((50, 24, 300), (20, 5, 20), (40, 8, 40)),     # 121 / 241 taps, radius 120 on 50 planes
     "c_one_plane": ((1, 33, 50), (4, 4, 4), (7, 7, 7)),
     "d_tile_edges": ((9, 31, 257), (1.5, 1.5, 1.5), (3, 3, 3)),
+    "s_staging": ((3, 5, 67), (1.5, 1.5, 1.5), (3, 3, 3)),           # no extent a multiple of any tile
 }
 
 
@@ -175,7 +176,15 @@ def test_weights_inside_fusion_are_the_stand_alone_weights(gpu):
     np.testing.assert_array_equal(got2, want2)
 
 
-def test_host_and_device_pointers_give_the_same_bits(gpu):
+def staged(img, on_device):
+    """a private copy of img where the call shall find it, and its address"""
+    import torch
+    a = torch.from_numpy(img.copy()).cuda() if on_device else img.copy()
+    torch.cuda.synchronize()   # the library runs on its own stream
+    return a, C.c_void_p(a.data_ptr() if on_device else a.ctypes.data)
+
+
+def test_host_and_device_pointers_give_the_same_bits(gpu, lib):
     import torch
     img, s1, s2, _, _ = case("a_multifold_z")
     host = content_based_weights(img, s1, s2)
@@ -183,6 +192,20 @@ def test_host_and_device_pointers_give_the_same_bits(gpu):
     assert dev.is_cuda
     np.testing.assert_array_equal(dev.cpu().numpy(), host)
     np.testing.assert_array_equal(content_based_weights(img, s1, s2), host)   # and run to run
+    # the C entry with every pairing of a host / device-resident image and result
+    img, s1, s2, w64, w32 = case("s_staging")
+    host = content_based_weights(img, s1, s2)
+    check_against_restatement("s_staging", host, w64, w32)
+    dims = (C.c_int64 * 3)(*img.shape[::-1])
+    sig = [(C.c_double * 3)(*s) for s in (s1, s2)]
+    for src_dev in (False, True):
+        for out_dev in (False, True):
+            src, sp = staged(img, src_dev)
+            out, op = staged(np.zeros_like(img), out_dev)
+            assert lib.spim_content_based_weights(sp, dims, sig[0], sig[1], op, 0) == 0
+            got = out.cpu().numpy() if out_dev else out
+            np.testing.assert_array_equal(got.view(np.uint32), host.view(np.uint32), err_msg=f"{src_dev} {out_dev}")
+            np.testing.assert_array_equal(src.cpu().numpy() if src_dev else src, img)   # the image is only read
 
 
 def test_old_entry_point_is_unchanged(gpu):
