@@ -719,6 +719,12 @@ int spim_min_max(const float* img, const int64_t dims[3], int device, float* min
  * volumes of scratch live in the workspace of spim_bbox_release_workspace. */
 int spim_min_filter(const float* img, const int64_t dims[3], int radius, int device, float* out);
 
+/* The tiling of the minimum filter and of the min / max reduction, for tests that straddle it:
+ * lines per block, outputs per line and block along the pass axis for a small radius, the
+ * same for a large one, the largest small radius, and the threads per block and the blocks of
+ * the min / max reduction.  Needs no GPU. */
+void spim_min_filter_tiles(int32_t sizes[6]);
+
 /* MinFilterThreshold.computeBoundingBox: per axis the smallest and largest index of the voxels
  * with (double)v > threshold.  With no such voxel the reference's integers come back
  * (bounds_min = dims, bounds_max = 0) and *found = 0. */

@@ -286,6 +286,7 @@ SIGNATURES = {
                                              _pf, _pf, _pf]),
     "spim_content_based_weights": (C.c_int, [C.c_void_p, _pi64, _pd, _pd, C.c_void_p, C.c_int]),
     "spim_content_tiles": (None, [C.POINTER(_i32)]),
+    "spim_min_filter_tiles": (None, [C.POINTER(_i32)]),
     "spim_fuse_weighted_average_content": (C.c_int, [C.c_int, C.POINTER(ViewSource), C.POINTER(FusionParams),
                                                      _pf, _pf, _pd, _pd, _pf]),
     "lrsim_create": (C.c_int, [_pi64, C.c_int, C.c_int, C.c_int, C.c_char_p, C.POINTER(C.c_void_p)]),

@@ -31,7 +31,7 @@ import numpy as np
 from . import _lib
 from ._lib import check
 
-__all__ = ["max_bounding_box", "min_max", "min_filter", "threshold_bounds", "segment_bounds",
+__all__ = ["max_bounding_box", "min_max", "min_filter", "min_filter_tiles", "threshold_bounds", "segment_bounds",
            "auto_bounding_box", "release_workspace", "MAX_RADIUS", "farthest_pair", "axis_boxes",
            "points_min_max", "preconcatenate", "reorient_bounding_box", "reorient_tile",
            "release_reorient_workspace"]
@@ -117,6 +117,15 @@ def min_filter(img, radius: int, device: int | None = None, out=None):
             optr = out.ctypes.data
     check(lib.spim_min_filter(C.c_void_p(ptr), dims, int(radius), dev, C.c_void_p(optr)))
     return out
+
+
+def min_filter_tiles():
+    """(lines per block, outputs per line and block along the pass axis for a small radius, the
+    same for a large one, the largest small radius, threads per reduction block, reduction
+    blocks) of the minimum filter and min / max kernels.  Needs no GPU."""
+    sizes = (C.c_int32 * 6)()
+    _lib.load().spim_min_filter_tiles(sizes)
+    return tuple(int(s) for s in sizes)
 
 
 def threshold_bounds(img, threshold: float, device: int | None = None):

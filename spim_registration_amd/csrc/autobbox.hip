@@ -494,6 +494,12 @@ extern "C" int spim_min_filter(const float* img, const int64_t dims[3], int radi
     return guarded([&] { min_filter(img, dims, radius, device, out); });
 }
 
+extern "C" void spim_min_filter_tiles(int32_t sizes[6]) {
+    if (!sizes) return;
+    const int32_t v[6] = {kMfLines, kMfTileSmall, kMfTileLarge, kMfSmallRadius, kRedBlock, kRedGrid};
+    std::copy(v, v + 6, sizes);
+}
+
 extern "C" int spim_threshold_bounds(const float* img, const int64_t dims[3], double threshold, int device,
                                      int64_t bounds_min[3], int64_t bounds_max[3], int32_t* found) {
     return guarded([&] { threshold_bounds(img, dims, threshold, device, bounds_min, bounds_max, found); });

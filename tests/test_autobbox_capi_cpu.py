@@ -91,6 +91,13 @@ def test_defaults_and_layout(lib):
     assert bb.MAX_RADIUS == 64
 
 
+def test_min_filter_tiles_needs_no_gpu(lib):
+    import autobbox_cases as ac
+    assert bb.min_filter_tiles() == (ac.LINES, ac.TILE_SMALL, ac.TILE_LARGE, ac.SMALL_RADIUS, ac.RED_BLOCK,
+                                     ac.RED_GRID) == (64, 64, 128, 16, 256, 1024)
+    lib.spim_min_filter_tiles(None)          # a null pointer is ignored
+
+
 def test_image_argument_errors(lib):
     """Argument errors come before the device is looked at: these hold with and without a GPU."""
     img = np.ones((3, 4, 5), np.float32)
