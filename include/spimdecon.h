@@ -602,6 +602,60 @@ int spim_icp_assign(const double* target, int64_t nt, const double* reference, i
                     int64_t* ambiguous);
 
 /* ======================================================================
+ * 6f. "Thin out detections" -- spim/fiji/plugin/ThinOut_Detections.java:73-166 (thinOut),
+ *     :238-299 (plotHistogram), spim/fiji/plugin/thinout/Histogram.java:56-90 (getMinMax,
+ *     binData).  Per detection of one view the distance to its nearest other detection in
+ *     calibrated units (l[d] * voxel[d]), in double; the detections whose distance lies in
+ *     [min_distance, max_distance] are removed, or they alone are kept.  Bit-exact against the
+ *     reference's arithmetic: s = ((dx dx) + (dy dy)) + (dz dz), every product and sum rounded
+ *     on its own, Math.sqrt of the smallest s.  Unpinned: imglib2's kd-tree is not in the
+ *     reference's tree; among equal s the lower index is the nearest here.  A list of one
+ *     point has no other point: distance +inf, nearest -1 (kept by remove-range, dropped by
+ *     keep-range).
+ * ====================================================================== */
+typedef struct spim_thinout_params {
+    double  min_distance;    /* 0   (ThinOut_Detections.java:38)                              */
+    double  max_distance;    /* 5   (:39)                                                     */
+    int32_t keep_range;      /* 0 = remove the range (:42), 1 = keep only the range            */
+    int32_t t_split;         /* 0 = auto; >0 forces that many partitions of the list (tests)   */
+    int32_t device;
+} spim_thinout_params;
+
+void spim_thinout_params_default(spim_thinout_params* p);
+
+/* The self-join kernel's tile sizes: points per block, points per LDS tile.  Host only: needs
+ * no GPU. */
+void spim_thinout_tiles(int32_t* row_block, int32_t* col_tile);
+
+/* dist[i] = the distance of point i of pts (n x 3 doubles, x y z; host or device memory) to its
+ * nearest other point after scaling by voxel (3 doubles, host), nearest[i] = that point's index
+ * (the self pair is left out by index: an exact duplicate is a neighbour at distance 0).  dist
+ * and nearest: n entries, host or device memory.  n == 0: status OK, nothing written.
+ * min_distance >= max_distance (or a NaN), a negative t_split, coordinates that are not finite
+ * (as double or float, before or after the scaling) or more than 2^31 - 1 points:
+ * SPIMDECON_ERR_ARG.  The result does not depend on t_split. */
+int spim_nn_distances(const double* pts, int64_t n, const double voxel[3], const spim_thinout_params* p,
+                      double* dist, int32_t* nearest);
+
+/* spim_nn_distances, and kept[0 .. *count) = the indices, ascending, of the points the range
+ * rule keeps (:141): keep_range d >= min && d <= max, else d < min || d > max.  Entry k is the
+ * detection with the new id k.  *count beyond cap: SPIMDECON_ERR_ARG, *count says how many
+ * there are (dist / nearest are written all the same).  n == 0: *count = 0, nothing else is
+ * touched. */
+int spim_thin_out(const double* pts, int64_t n, const double voxel[3], const spim_thinout_params* p,
+                  double* dist, int32_t* nearest, int32_t* kept, int64_t cap, int64_t* count);
+
+/* Histogram.getMinMax and binData over the n distances (host or device memory) whose
+ * select_or_null[i] != 0 (null: all of them): *min, *max, counts[num_bins] of
+ * bin = (int) floor(((v - min) / size) * num_bins) with size = (max - min) + 0.000001, and the
+ * bin centres[num_bins] = min + binSize / 2 + binSize * bin, binSize = size / num_bins.
+ * SPIMDECON_ERR_ARG: num_bins < 1 or > 4096, n < 2, an empty selection, a selected distance
+ * that is not finite, a distance that falls into bin num_bins (Java's
+ * ArrayIndexOutOfBoundsException, when max - min absorbs the 0.000001). */
+int spim_distance_histogram(const double* dist, int64_t n, const uint8_t* select_or_null, int32_t num_bins,
+                            int device, double* min, double* max, int64_t* counts, double* centres);
+
+/* ======================================================================
  * 7. Deconvolution input preparation --
  *    spim/process/fusion/deconvolution/ProcessForDeconvolution.java:159-384:
  *    each view resampled into the fused bounding box through the inverse of

@@ -104,6 +104,16 @@ class IcpParams(C.Structure):
     ]
 
 
+class ThinOutParams(C.Structure):
+    _fields_ = [
+        ("min_distance", C.c_double),
+        ("max_distance", C.c_double),
+        ("keep_range", C.c_int32),
+        ("t_split", C.c_int32),
+        ("device", C.c_int32),
+    ]
+
+
 class Peak(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("z", C.c_int32),
                 ("intensity", C.c_float), ("is_min", C.c_int32), ("is_max", C.c_int32)]
@@ -245,6 +255,12 @@ SIGNATURES = {
     "spim_icp_tiles": (None, [C.POINTER(_i32), C.POINTER(_i32)]),
     "spim_icp_assign": (C.c_int, [C.c_void_p, _i64, C.c_void_p, _i64, C.c_void_p, C.POINTER(IcpParams), C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, _i64, _pi64, _pi64]),
+    "spim_thinout_params_default": (None, [C.POINTER(ThinOutParams)]),
+    "spim_thinout_tiles": (None, [C.POINTER(_i32), C.POINTER(_i32)]),
+    "spim_nn_distances": (C.c_int, [C.c_void_p, _i64, _pd, C.POINTER(ThinOutParams), C.c_void_p, C.c_void_p]),
+    "spim_thin_out": (C.c_int, [C.c_void_p, _i64, _pd, C.POINTER(ThinOutParams), C.c_void_p, C.c_void_p,
+                                C.c_void_p, _i64, _pi64]),
+    "spim_distance_histogram": (C.c_int, [C.c_void_p, _i64, C.c_void_p, _i32, C.c_int, _pd, _pd, _pi64, _pd]),
     "spim_psf_release_workspace": (C.c_int, [C.c_int]),
     "spim_save_interest_points": (C.c_int, [C.c_char_p, C.c_char_p, C.POINTER(InterestPointC),
                                             C.POINTER(C.c_int32), C.c_int64]),

@@ -123,7 +123,7 @@ def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 
                       downsample_xy=1, downsample_z: int = 1, voxel_size=None,
                       max_detections: int | None = None,
                       max_detections_type: str = "brightest", auto_bb: dict | None = None,
-                      reorient: dict | None = None) -> TimepointResult:
+                      reorient: dict | None = None, thin_out: dict | None = None) -> TimepointResult:
     """views: per view a [z, y, x] float32 torch tensor on the GPU (the acquired
     stack); models: 3x4 view -> world affines; bb_min / bb_dims (x, y, z), or bb_min="auto"
     (bb_dims None): the box is estimated from the views under the models the input preparation
@@ -155,7 +155,12 @@ def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 
     (``downsample.downsample``, DifferenceOf.openAndDownsample) and ``points`` are corrected to
     pixels of the full views, so every later stage is untouched; ``ms["downsample"]`` is that
     pass alone and is part of ``ms["detect"]``; max_detections / max_detections_type
-    ('brightest', 'median', 'weakest'): ``downsample.limit_detections`` per view."""
+    ('brightest', 'median', 'weakest'): ``downsample.limit_detections`` per view; thin_out (a
+    dict with min_distance, max_distance and keep_range, by default 0, 5 and False):
+    ``thinout.thin_out`` per view after that limit and before every later stage, in the units of
+    voxel_size ((1, 1, 1) when that is None), the counts before and after logged per view
+    (ThinOut_Detections.java:154-155); ``ms["thin_out"]`` is that step alone and is part of
+    ``ms["detect"]``; None (the default): the step is not run."""
     import torch
     from . import downsample as ds
     ds_z = ds.downsample_factor(downsample_z)
@@ -163,6 +168,21 @@ def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 
     if max_detections_type not in ds.LIMIT_KINDS:
         raise ValueError(f"max_detections_type must be 'brightest', 'median' or 'weakest', not "
                          f"{max_detections_type!r}")
+    to_kw = None
+    if thin_out is not None:
+        from . import thinout
+        if not isinstance(thin_out, dict):
+            raise ValueError("thin_out must be None or a dict with min_distance, max_distance and keep_range")
+        unknown = sorted(set(thin_out) - {"min_distance", "max_distance", "keep_range"})
+        if unknown:
+            raise ValueError(f"thin_out: unknown keys {unknown}")
+        to_range = float(thin_out.get("min_distance", 0.0)), float(thin_out.get("max_distance", 5.0))
+        thinout.check_range(*to_range)
+        to_voxel = (1.0, 1.0, 1.0) if voxel_size is None else tuple(float(x) for x in voxel_size)
+        if len(to_voxel) != 3:
+            raise ValueError("voxel_size must be (x, y, z)")
+        to_kw = dict(voxel_size=to_voxel, min_distance=to_range[0], max_distance=to_range[1],
+                     keep_range=bool(thin_out.get("keep_range", False)), device=device)
     if icp and refine is None:
         raise ValueError("icp=True needs refine (the model of the ICP registration)")
     if detector not in ("dog", "dom"):
@@ -193,7 +213,7 @@ def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 
     torch.cuda.synchronize(device)
     t = time.perf_counter()
     points = []
-    t_ds = 0.0
+    t_ds = t_to = 0.0
     for v in views:          # 1. ProcessDOG (or ProcessDOM) per view, read in place
         if (ds_xy, ds_z) != (1, 1):   # (the call returns after its stream has drained)
             t0 = time.perf_counter()
@@ -211,9 +231,18 @@ def process_timepoint(views, models, bb_min, bb_dims=None, *, psf_size=(19, 19, 
         if max_detections is not None:
             pos, _ = ds.limit_detections(pos, inten, max_detections, max_detections_type)
             pos = np.ascontiguousarray(pos)
+        if to_kw is not None:   # "Thin out detections", per view
+            t0 = time.perf_counter()
+            before = len(pos)
+            pos = np.ascontiguousarray(thinout.thin_out(pos, **to_kw))
+            t_to += time.perf_counter() - t0
+            if log:
+                log(f"thin out: view {len(points)}, detections: {before} >>> {len(pos)}")
         points.append(pos)
     if (ds_xy, ds_z) != (1, 1):
         ms["downsample"] = round(t_ds * 1e3, 2)
+    if to_kw is not None:
+        ms["thin_out"] = round(t_to * 1e3, 2)
     t = lap("detect", t)
     gres = None
     models = [np.asarray(m, np.float64).reshape(3, 4) for m in models]
